@@ -14,7 +14,15 @@ K1's 42 us on one MI355X: `--mixdown fused` at N = 1 shows it); `--mixdown off|f
 `--workload config3|config4|config5` runs the other BASELINE configs through the same harness and JSON shape (same
 unit; SURVEY 8d: a "sample" is one voice output, one FFT input sample, one grain-sample).
 
-Prints ONE JSON line on rank 0: metric/value/unit/..., plus
+A plain run sets up, warms up, times --steps steps, writes what the last timed step computed if --dump-outputs DIR is given
+(DIR/<name>.npy, large outputs as a seeded sample), and prints ONE JSON line on rank 0: metric/value/unit/ms_per_step/..., with
+the roofline of the dominant kernel taken from the timed steps themselves: without the per-kernel event pass, a step of several
+kernels (tables, config 4's two-kernel route, the mixdown forms) is charged to its dominant kernel whole (`roofline.timing` says
+so), so its roofline.kernel_ms / frac do not compare with a --full line's.  Before the warm-up, the state each workload carries
+from step to step is put back to where the workload was built (the clock ramp runs for a wall-clock time), so the timed steps
+of config 3 and 5 start from the first block of their gate / grain schedules.  Everything measured beyond that runs only with
+--full: the per-kernel event pass, the CPU baseline, the write / read ceilings, the 131 072-voice bank, the other configs
+(`configs`) and, with N > 1, the step without the reduce.  With --full the line carries
   "roofline"      the dominant kernel against the 8 TB/s HBM peak (or the fp64 MFMA peak for --mfcc-method mfma):
                   algorithmic bytes per launch / average launch duration, the duration measured with HIP events the
                   library records around that kernel on its launch stream (mxg_prof_*) inside the timed region;
@@ -107,6 +115,35 @@ def share_estimate(kernels, dom, step_ms):
 ESTIMATOR = ("single-kernel step: GPU-side step time (two HIP events around the timed steps, no markers inside) / launches per step = an "
              "upper bound on the average launch duration (launch gaps included); step of several kernels: HIP events around this "
              "kernel's own launches (marker pair included: conservative), never more than the step")
+
+
+DUMP_SEED = 0x4D415849
+DUMP_ARRAY_BYTES = 16 << 20   # per array: a larger output is written as a fixed, seeded sample of its rows or columns
+DUMP_TOTAL_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: write each output (name -> float64 / float32 torch tensor) as out_dir/<name>.npy.  An output of more
+    than DUMP_ARRAY_BYTES keeps a seeded choice of whole rows or columns along its longer axis, and those indices go beside it
+    as <name>_index.npy (float64), so that two builds given the same arguments write comparable files."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in outs.items():
+        arrays = {}
+        if t.numel() * t.element_size() > DUMP_ARRAY_BYTES:
+            axis = 0 if t.dim() == 1 or t.shape[0] >= t.shape[1] else 1
+            n = t.shape[axis]
+            k = max(1, DUMP_ARRAY_BYTES // (t.numel() // n * t.element_size()))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+            arrays[name + "_index"] = idx.astype(np.float64)
+        arrays[name] = t.cpu().numpy()
+        for nm, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64), (nm, a.dtype)
+            total += a.nbytes
+            assert total <= DUMP_TOTAL_BYTES, "--dump-outputs: more than %d bytes" % DUMP_TOTAL_BYTES
+            np.save(os.path.join(out_dir, nm + ".npy"), a)
 
 
 def _sig(x, n=5):
@@ -226,9 +263,21 @@ def main():
     ap.add_argument("--verbose", action="store_true",
                     help="print the long form of the line (full workload texts, estimator notes, per-kernel tables in every `configs` entry); "
                          "the default line is the compact form (< 7000 characters: the driver keeps an 8 KB tail)")
-    ap.add_argument("--kernel-events", default="pass", choices=["inline", "pass", "off"],
-                    help="per-kernel HIP events inside the timed region (inline), in a separate pass, or not at all")
+    ap.add_argument("--kernel-events", default=None, choices=["inline", "pass", "off"],
+                    help="per-kernel HIP events inside the timed region (inline), in a separate pass, or not at all (default: pass "
+                         "with --full, else off)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else the line can carry: the per-kernel event pass, the CPU "
+                         "baseline, the write / read ceilings, the 131 072-voice bank, the other configs, the step without the reduce "
+                         "(N > 1); --no-cpu-baseline, --no-extras and --no-configs take parts of it out again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; an output over "
+                         "16 MB as a seeded sample of its rows or columns, with <name>_index.npy)")
     args = ap.parse_args()
+    if args.kernel_events is None:
+        args.kernel_events = "pass" if args.full else "off"
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = args.no_configs = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become the launcher.  One process per GPU under torch.distributed.run
         # (the same command line the driver uses for N > 1); rank 0 prints the JSON line.
@@ -321,6 +370,42 @@ def main():
         if world > 1 and comm is None and (force_torch or not args.share_gpu):
             return TorchMixQueue(dist, block_doubles, depth, 0, stream, dev, groups=groups)
         return RcclMixQueue(comm, block_doubles, depth, 0, stream, groups=groups)
+
+    def keep_state(*bufs):
+        """A copy of the state a workload carries from step to step (torch tensors or DeviceBuffers), taken now, and a function that
+        puts it back in stream order.  The clock ramp runs for a wall-clock time, so without it the warm-up and the timed steps -- and
+        what --dump-outputs writes -- would start from a state that depends on how fast the ramp went."""
+        def ref(b):
+            return (b.data_ptr(), b.numel() * b.element_size()) if isinstance(b, torch.Tensor) else (b.ptr, b.nbytes)
+        saved = []
+        for b in bufs:
+            p, n = ref(b)
+            c = torch.empty(n, dtype=torch.uint8, device=dev)
+            chk(L.mxg_memcpy_d2d_async(c.data_ptr(), p, n, stream), "mxg_memcpy_d2d_async")
+            saved.append(c)
+
+        def restore():
+            for b, c in zip(bufs, saved):
+                p, n = ref(b)
+                chk(L.mxg_memcpy_d2d_async(p, c.data_ptr(), n, stream), "mxg_memcpy_d2d_async")
+        return restore
+
+    def as_tensor(b):
+        """A DeviceBuffer's contents as a torch tensor (a copy in stream order)."""
+        t = torch.empty(b.shape, dtype=torch.float64, device=dev)
+        chk(L.mxg_memcpy_d2d_async(t.data_ptr(), b.ptr, b.nbytes, stream), "mxg_memcpy_d2d_async")
+        return t
+
+    def last_mix(q):
+        """The [B][2] stereo mix of the last block pushed to q, as the root receives it (q flushed)."""
+        if hasattr(q, "result"):
+            p, nb, _ = q.result()
+            assert p and nb, "the mix queue holds no block"
+            t = torch.empty(q.block, dtype=torch.float64, device=dev)
+            chk(L.mxg_memcpy_d2d_async(t.data_ptr(), p + (nb - 1) * q.block * 8, q.block * 8, stream), "mxg_memcpy_d2d_async")
+        else:
+            t = torch.from_numpy(q.result_numpy()[-1].copy())
+        return t.reshape(-1, 2)
 
     V, B = (args.voices or VOICES_PER_GPU), BLOCK
     nbuf = args.out_buffers if args.out_buffers > 0 else max(1, -(-(1 << 31) // (V * B * 8)))
@@ -415,6 +500,9 @@ def main():
                      tag="configs[1]: %d-voice maxiOsc::%s bank, block 512, out[n][v] stored%s, %d rotated buffers"
                          % (V, args.waveform, {"fused": " + fused stereo mixdown", "separate": " + K3 mixdown", "off": ""}[mixdown], nbuf),
                      local_step=bank.with_queue(local_queue).step if local_queue is not None else None,
+                     restart=keep_state(bank.phase, bank.hold),
+                     outputs=lambda: dict(({} if args.mix_only and mixdown == "fused" else {"out": bank.outs[(bank.i - 1) % len(bank.outs)]}),
+                                          phase=bank.phase),
                      workload="configs[1]: %d-voice maxiOsc::%s wavetable bank per GPU, block=512, fp64 out[n][v] stored%s, output "
                               "rotated over %d block buffer(s) = %.2f GB touched before a line is rewritten"
                               % (V, args.waveform, {"fused": " + fused maxiMix::stereo mixdown", "separate": " + K3 mixdown",
@@ -444,18 +532,30 @@ def main():
             if t_queue:
                 queue = make_queue(B * 2, args.mix_depth, Gt)
 
+            plain_next = [False]  # set by the restart: the next render goes without MXG_TABLES_AHEAD
+
             def render_tables(rows_ptr, mix_ptr):
                 # round 6: pipelined blocks -- the next block's phase recurrence walks beside this block's table traffic (tables_ahead=0:
                 # round 5's marks kernel in front of every render); tables_sum=1: the row sum inside the render kernel
                 chk(L.mxg_osc_render_tables_ex(Vt, B, ft.data_ptr(), tabs.data_ptr(), pht.data_ptr(), hdt.data_ptr(), None, pt.data_ptr(),
-                                               rows_ptr, mix_ptr, t_ahead, stream), "mxg_osc_render_tables_ex")
+                                               rows_ptr, mix_ptr, 0 if plain_next[0] else t_ahead, stream), "mxg_osc_render_tables_ex")
+                plain_next[0] = False
 
             def step_plain():
                 render_tables(rowst.data_ptr(), mixt.data_ptr() if t_sum else None)
                 if not t_sum:
                     chk(L.mxg_mix_rows_sum(Gt, B * 2, rowst.data_ptr(), mixt.data_ptr(), stream), "mxg_mix_rows_sum")
             step_tables = MixdownStep(lambda slot: render_tables(slot, None), queue) if t_queue else step_plain
+            restore_tables = keep_state(pht, hdt)
+
+            def restart_tables():
+                # the pipelined form keeps the next block's start phase and marks in the library's per-stream context, on the promise
+                # that d_phase is not written between calls (include/maxigpu.h); the restore writes it, so the next call goes without the
+                # flag: same bits, and the library drops that context and starts over from the restored d_phase
+                restore_tables()
+                plain_next[0] = True
             W = dict(step=step_tables, samples=Vt * B, dominant="osctab_kernel", algo_bytes=Vt * (514 * 8.0 + 24.0), dtype="f64", cpu=None,
+                     restart=restart_tables, outputs=lambda: dict(phase=pht, **({} if t_queue else {"mix": mixt})),
                      tag="EXTENSION: %d-voice sinebuf bank, one 514-entry table PER VOICE (HBM-read form), fused mixdown out" % Vt,
                      local_step=None,
                      workload="EXTENSION of configs[1] (not in the reference, which has one shared sineBuffer): %d-voice maxiOsc::sinebuf bank "
@@ -504,7 +604,8 @@ def main():
                 return {"unit": "Msamples/s", "kind": kind, "value": round(Vc * Nc / dt / 1e6, 2), "cores": 1,
                         "sample": "maxiSample::playAtSpeed, %d heads x %d samples over a 4 Mi-element sample, one thread; %.2f s wall" % (Vc, Nc, dt)}
             W = dict(step=step_sample, samples=Vs * B, dominant="sample_parts_kernel", algo_bytes=(16.0 + 24.0 / B) * Vs * B, dtype="f64", cpu=cpu,
-                     local_step=None, keep=(arena,), traffic_key="sample_parts_kernel@sample_bank",
+                     local_step=None, keep=(arena,), traffic_key="sample_parts_kernel@sample_bank", restart=keep_state(d_pos),
+                     outputs=lambda: dict(out=as_tensor(outs_s[(kb[0] - 1) % len(outs_s)]), position=as_tensor(d_pos)),
                      tag="maxiSample::playAtSpeed, %d heads over one 8.6 GB sample (HBM-resident: each head its own region), block 512" % Vs,
                      workload="north_star's sample path where the sample cannot live on chip: %d play heads of maxiSample::playAtSpeed over one "
                               "%.1f GB sample, heads %d elements apart, speeds over [0.5, 1.5) (mean 1: 8 B read + 8 B written per sample), "
@@ -563,7 +664,13 @@ def main():
             algo3 = (8.0 + 176.0 / B) * V * B
             if mixdown == "fused":
                 algo3 += 8.0 * V + 16.0 * B * (V / 256.0)  # + pan read, per-workgroup mix rows written
+            restore3 = keep_state(vb.osc_state, vb.flt_state, vb.env.dstate, vb.env.istate)
+
+            def restart3():
+                restore3()
+                blk[0] = 0
             W = dict(step=step, samples=V * B, dominant="voice_kernel", algo_bytes=algo3, dtype="f64", cpu=cpu,
+                     restart=restart3, outputs=lambda: dict(out=as_tensor(outs3[(blk[0] - 1) % nbuf])),
                      traffic_key="voice_kernel@config3_modB" if mode == 1 else ("voice_kernel@config3_mix" if mixdown == "fused" else None),
                      tag="configs[2]: %d voices saw->lores->adsr (mode %s), block 512%s" % (V, "AB"[mode], {"fused": " + fused stereo mixdown",
                                                                                                        "separate": " + K3 mixdown", "off": ""}[mixdown]),
@@ -633,6 +740,7 @@ def main():
                                                                            stream), "calib_read"), 6, warm=3)
                 return out
             W = dict(step=step, samples=NF * 1024, dtype="f32 (FFT) / f64 (MFCC)", cpu=cpu, read_ceiling=read_ceiling if fused_ok else None,
+                     outputs=lambda: dict(mfcc=mfcc),
                      dominant="mfcc_mfma_gemm_kernel" if mfma else ("fft_mfcc_kernel" if fused_ok else "fft1024_kernel"),
                      traffic_key="fft_mfcc_kernel@config4_mfma" if mm else ("fft_mfcc_kernel@config4_walk" if mfcc_method == "walk" else None),
                      tag="configs[3]: maxiFFT(1024)+maxiMFCC(512,42,13) x %d frames, %s" % (NF, "FFT kernel + dense MFMA GEMM" if mfma else (
@@ -693,6 +801,7 @@ def main():
                                  (256, 8 * 70560), "samples per stream", "%d maxiTimeStretch<hann> streams, play(speed,0.05,4), stream-inner "
                                  "loop, 4 grain-samples per stream-sample" % Sc, target_s)
             W = dict(step=step, samples=S * T * 4, dominant="granular_unit_kernel", algo_bytes=(8.0 * 4 + 8.0) * S * T, dtype="f64", cpu=cpu,
+                     restart=keep_state(gb.state, gb.grains), outputs=lambda: dict(out=as_tensor(out5)),
                      tag="configs[4]: %d maxiTimeStretch<hann> streams x %d samples, 4 overlaps%s" % (S, T, "" if mixdown == "off" else " + stereo mixdown"),
                      # what the render actually moves, all of it from L2 / Infinity Cache (the 35 MB sample and the 17.6 KB window are resident):
                      # per stream-sample 4 live grains x (buffer[a], buffer[a+1] = 16 B + 8 B of window) + the 8-byte store
@@ -746,6 +855,8 @@ def main():
             go = bool(int(flag.item()))
         if not go:
             break
+    if W.get("restart"):
+        W["restart"]()  # the ramp leaves no trace: the warm-up starts from the state the workload was built with
     for _ in range(args.warmup):
         step()
     if queue is not None:
@@ -765,6 +876,11 @@ def main():
     fence()
     t1 = time.perf_counter()
     L.mxg_prof_enable(0)
+    if args.dump_outputs and rank == 0:  # what the last timed step computed, before anything else runs
+        outs = W["outputs"]()
+        if queue is not None:
+            outs["mix"] = last_mix(queue)
+        dump_outputs(outs, args.dump_outputs)
     if os.environ.get("MXG_PRINT_PACE") and args.workload == "config2":  # (diagnostics: K1's pace controllers, csrc/mxg_pace.h)
         buf = (ctypes.c_uint * 128)()
         L.mxg_debug_osc_pace(ctypes.c_void_p(stream), buf)
@@ -812,7 +928,7 @@ def main():
 
     # ---- N > 1: the SAME step with the reduce taken out (mix queue without a communicator), same run, same buffers ----
     local_ms = None
-    if W.get("local_step") is not None:
+    if args.full and W.get("local_step") is not None:
         fence()
         ls = W["local_step"]
         nl = max(10, min(args.steps, 400))

@@ -2,9 +2,10 @@
 and fail -- if it has to -- only on the number of GPUs, never on how it was started.
 
 CPU part (-m "not gpu"): without any GPU every rank stops at "needs a HIP device", after the launcher has spawned both.
-GPU part (-m gpu, one MI355X): (a) `--gpus 2` reaches the device-count check of rank 1 and says so; (b) `--gpus 2 --share-gpu`
+GPU part (-m gpu, one MI355X): (a) `--gpus 2` reaches the device-count check of rank 1 and says so; (b) `--gpus 2 --share-gpu --full`
 runs the whole two-rank harness on the one device (gloo carries the barriers, the mix queue reduces locally) and prints the one
-JSON line with n_gpus = 2, per_gpu_efficiency and value_like_for_like_n1."""
+JSON line with n_gpus = 2, per_gpu_efficiency and value_like_for_like_n1; (c) a plain run prints the headline fields only and
+--dump-outputs writes the same files twice."""
 import json
 import os
 import subprocess
@@ -51,7 +52,7 @@ def test_two_ranks_on_a_one_gpu_box_fail_only_at_the_device_count():
 
 @pytest.mark.gpu
 def test_two_ranks_sharing_one_gpu_print_the_scaling_fields():
-    r = _run(["--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "8", "--no-cpu-baseline"])
+    r = _run(["--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "8", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -78,7 +79,7 @@ def test_two_ranks_with_the_fallback_exchange():
     """bench.py's safety net for a multi-GPU node on which mxg_comm_create fails: the same step with torch tensors as staging and
     torch.distributed.reduce as the sum (maximilian_amd.dist.TorchMixQueue), forced here over gloo with two ranks on one GPU; the
     line says so."""
-    r = _run(["--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "8", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "8", "--no-cpu-baseline", "--full"],
              env={"MXG_BENCH_FORCE_TORCH_EXCHANGE": "1"})
     assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -89,10 +90,10 @@ def test_two_ranks_with_the_fallback_exchange():
 
 
 @pytest.mark.gpu
-def test_default_line_carries_every_gpu_config():
-    """The command the driver runs (`bench.py --gpus 1 --steps K --warmup W`) reports configs 3, 4, 4-mfma, 5 and the fused-mixdown
-    step next to the headline: each with its own ms_per_step, value and the roofline of its dominant kernel."""
-    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=1200)
+def test_full_line_carries_every_gpu_config():
+    """`bench.py --gpus 1 --steps K --warmup W --full` reports configs 3, 4, 4-mfma, 5 and the fused-mixdown step next to the
+    headline: each with its own ms_per_step, value and the roofline of its dominant kernel."""
+    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], timeout=1200)
     assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -127,3 +128,60 @@ def test_default_line_carries_every_gpu_config():
     # config 3's N > 1 step on one GPU (K2f with the mixdown fused, producer / consumer wavefronts): VERDICT r05 #1 asks <= 1.15 x config 3's
     # own step (measured 1.10); the guard leaves room for a box's mood
     assert d["configs"]["config3_mixdown"]["step_vs_config3"] < 1.25, d["configs"]["config3_mixdown"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("steps", [30, 40])
+def test_plain_line_and_dumped_outputs(tmp_path, port, steps):
+    """A plain run (`bench.py --gpus 1 --steps K --warmup W`) prints the headline without anything that takes runs of its own, and
+    renders exactly W + K blocks from the state the bank was built with (the clock ramp before the warm-up runs for a wall-clock
+    time and leaves no trace): what --dump-outputs writes -- the last block and the carried phase -- is the oracle's after W + K
+    blocks, bit for bit, for two values of K."""
+    import numpy as np
+    from maximilian_amd import OSC_WAVEFORMS
+    from maximilian_amd.dist import bank_parameters
+    W = 5
+    d_out = str(tmp_path / "dump")
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(W), "--dump-outputs", d_out], timeout=300)
+    assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == W and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "Msamples/s" and d["dtype"] == "f64" and d["roofline"]["kernel"] == "osc_kernel"
+    assert "configs" not in d and "cpu_baseline" not in d and "north_star_bank" not in d and not d.get("kernels")
+    names = sorted(os.listdir(d_out))
+    assert names == ["out.npy", "out_index.npy", "phase.npy"], names
+    got = {n[:-4]: np.load(os.path.join(d_out, n)) for n in names}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    out, idx, phase = got["out"], got["out_index"], got["phase"]
+    assert out.dtype == np.float64 and out.shape == (512, idx.size) and phase.shape == (65536,)
+    # the oracle over 256 of the sampled voices, block after block from phase 0
+    sel = np.arange(0, idx.size, idx.size // 256)
+    v = idx[sel].astype(np.int64)
+    freq = bank_parameters(0, 65536, 65536)[0][v]
+    ph, hold = None, None
+    for _ in range(W + steps):
+        blk, ph, hold = port.osc(OSC_WAVEFORMS["sinebuf"], freq, 512, phase=ph, hold=hold)
+    assert np.array_equal(phase[v].view(np.uint64), ph.view(np.uint64))
+    assert np.array_equal(out[:, sel].view(np.uint64), blk.view(np.uint64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("args", [["--workload", "tables"], ["--workload", "config3"], ["--workload", "sample_bank"],
+                                  ["--workload", "config5"], ["--mixdown", "fused"]], ids=lambda a: "-".join(x.strip("-") for x in a))
+def test_dumped_outputs_repeat(tmp_path, args):
+    """Every workload's carried state (phases, the pipelined tables render's context, envelopes and gate position, play heads, grain
+    states, the mix queue) is back where the workload was built before the warm-up: two runs with the same arguments dump the same
+    bits, however many steps each one's clock ramp took."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d_out = str(tmp_path / ("run%d" % i))
+        r = _run(args + ["--gpus", "1", "--steps", "12", "--warmup", "3", "--dump-outputs", d_out], timeout=300)
+        assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
+        dumps.append({n: np.load(os.path.join(d_out, n)) for n in sorted(os.listdir(d_out))})
+    assert dumps[0] and sorted(dumps[0]) == sorted(dumps[1])
+    for n, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).any(), n
+        assert np.array_equal(a.view(np.uint8), dumps[1][n].view(np.uint8)), n

@@ -1,6 +1,6 @@
-"""GPU (-m gpu): the DROP-IN boundary.  host/dropin_{01,14,15} are the reference's own example patches --
+"""GPU (-m gpu): the DROP-IN boundary.  oracle/_ref/dropin_{01,14,15} are the reference's own example patches --
 cpp/commandline/main.cpp (BASELINE config 1), maximilian_examples/14.monosynth/main.cpp and 15.polysynth/main.cpp --
-compiled VERBATIM (host/Makefile, where /root/reference exists) against include/maximilian.h, whose maxiOsc / maxiEnv /
+compiled VERBATIM (oracle/Makefile, into oracle/_ref/dropin_*) against include/maximilian.h, whose maxiOsc / maxiEnv /
 maxiFilter run on the GPU through the C-ABI, and driven by mxg_host_render (the loop of cpp/commandline/player.cpp:25-44).
 Expected samples: tests/golden/dropin.npz, dumped from the SAME source files linked with the unmodified reference
 library (oracle/example_host.cpp).  14 and 15 must match bit for bit (pulse / sinebuf / phasor oscillators, the lores
@@ -18,10 +18,19 @@ from conftest import ROOT, assert_bits_equal, ulp_diff
 pytestmark = pytest.mark.gpu
 
 
-def run_dropin(ex, frames, tmp_path, cwd=None, stdout=subprocess.DEVNULL):
-    exe = os.path.join(ROOT, "host", "dropin_" + ex)
+def dropin_exe(ex):
+    """The project's own patches (tests/patches, tags p1..p6) are built by host/Makefile; the reference's example patches need the
+    reference sources and are built by oracle/Makefile into oracle/_ref/, which is kept where those sources are absent."""
+    rel = os.path.join("host" if ex.startswith("p") else os.path.join("oracle", "_ref"), "dropin_" + ex)
+    exe = os.path.join(ROOT, rel)
     if not os.path.exists(exe):
-        pytest.fail("host/dropin_%s is not built (python -c 'import __graft_entry__ as g; g.build()' where /root/reference exists)" % ex)
+        pytest.fail("%s is not built (python -c 'import __graft_entry__ as g; g.build()' builds it; oracle/_ref/ needs the reference "
+                    "sources at build time)" % rel)
+    return exe
+
+
+def run_dropin(ex, frames, tmp_path, cwd=None, stdout=subprocess.DEVNULL):
+    exe = dropin_exe(ex)
     out = str(tmp_path / ("dropin_%s.f64" % ex))
     r = subprocess.run([exe, str(frames), out], stdout=stdout, stderr=subprocess.PIPE, text=True, timeout=900, cwd=cwd)
     assert r.returncode == 0, r.stderr
@@ -69,7 +78,7 @@ def test_signal_arguments_are_predicted_per_sample(tmp_path, ex, frames, max_lau
     got, log = run_dropin(ex, frames, tmp_path)
     n_on = _launches(log)
     env = dict(os.environ, MXG_PS_DERIVE="0")
-    exe = os.path.join(ROOT, "host", "dropin_" + ex)
+    exe = dropin_exe(ex)
     out2 = str(tmp_path / "off.f64")
     r = subprocess.run([exe, str(frames), out2], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr
@@ -81,7 +90,7 @@ def test_signal_arguments_are_predicted_per_sample(tmp_path, ex, frames, max_lau
     assert n_off >= 5 * n_on, "the patch was expected to need one launch per call without the prediction"
 
 
-# ten more of the reference's own example patches, compiled verbatim (host/Makefile dropin_<tag>): what each one exercises and
+# ten more of the reference's own example patches, compiled verbatim (oracle/Makefile _ref/dropin_<tag>): what each one exercises and
 # how closely it can match.  Patches built only from the wavetable / ramp oscillators, the envelope and the filter are
 # bit-identical; a sinewave is within 1 ULP of glibc's, so sums / products of sinewaves carry a few ULP, and where a sinewave
 # drives another oscillator's FREQUENCY (FM) the carrier's phase inherits that last-bit difference and integrates it.

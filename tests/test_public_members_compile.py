@@ -19,11 +19,13 @@ def test_public_members_patch_compiles_against_the_drop_in_header(tmp_path):
 
 
 def test_public_members_patch_is_valid_reference_code():
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference is not mounted here")
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I" + ref, PATCH], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-4000:]
+    # oracle/Makefile's _ref/example_p5 is this patch compiled against the unmodified reference sources (and linked with them)
+    exe = os.path.join(ROOT, "oracle", "_ref", "example_p5")
+    if not os.path.exists(exe):
+        pytest.skip("oracle/_ref/example_p5 not built (needs the reference sources at build time)")
+    syms = subprocess.run(["nm", "-C", exe], capture_output=True, text=True, timeout=300).stdout
+    assert " T setup()" in syms and " T play(double*)" in syms
+    assert "mxg_" not in syms   # the reference's own classes, not the drop-in header's
 
 
 def test_no_exceptions_build_of_the_header(tmp_path):

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/ab
 A=$1; B=$2
 for round in 1 2 3; do for lib in $A $B; do for ex in 1 0; do
-  MXG_LIB=$GRAFT_REPO_ROOT/$lib timeout 300 python bench.py --workload config4 --no-cpu-baseline --no-extras --steps 20 --warmup 5 --tune fft_exact=$ex 2>/dev/null | python -c "
+  MXG_LIB=$PWD/$lib timeout 300 python bench.py --full --workload config4 --no-cpu-baseline --no-extras --steps 20 --warmup 5 --tune fft_exact=$ex 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 wf=$1; shift
 for round in 1 2 3; do for lib in "$@"; do
-  MXG_LIB=$GRAFT_REPO_ROOT/$lib timeout 300 python bench.py --waveform $wf --no-cpu-baseline --no-extras --steps 300 --warmup 30 2>/dev/null | python -c "
+  MXG_LIB=$PWD/$lib timeout 300 python bench.py --full --waveform $wf --no-cpu-baseline --no-extras --steps 300 --warmup 30 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

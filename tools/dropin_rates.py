@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/dropin_rates.py -- real-time factor of the DROP-IN boundary: every host/dropin_* binary (a reference patch compiled verbatim
+"""tools/dropin_rates.py -- real-time factor of the DROP-IN boundary: every dropin_* binary (a reference patch compiled verbatim
 against include/maximilian.h, one C++ call per sample, blocks rendered on the GPU behind it) is run for a few seconds of audio;
 frames per second, launches per frame and the ratio to 44 100 frames/s are tabulated next to the same patch linked with the
 reference itself (oracle/_ref/example_*: the compiled reference on this host's CPU, present where /root/reference was at build time).
@@ -45,7 +45,8 @@ with tempfile.TemporaryDirectory() as td:
     shutil.copy(wav, os.path.join(td, "beat2.wav"))
     shutil.copy(wav, os.path.join(cwd, "mono.wav"))
     for tag, name in NAMES.items():
-        exe = os.path.join(ROOT, "host", "dropin_" + tag)
+        # (the project's own patches are built by host/Makefile, the reference's by oracle/Makefile into oracle/_ref/)
+        exe = os.path.join(ROOT, "host" if tag.startswith("p") else os.path.join("oracle", "_ref"), "dropin_" + tag)
         if not os.path.exists(exe):
             continue
         out = os.path.join(td, "o.f64")

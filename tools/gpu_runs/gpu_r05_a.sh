@@ -6,12 +6,12 @@ timeout 900 python -m pytest tests/test_gpu_spectral.py tests/test_gpu_osctab.py
 timeout 600 python tools/fused_ab.py > $O/fused_ab.log 2>&1; tail -14 $O/fused_ab.log
 for round in 1 2; do
   for lib in maximilian_amd/libmaxigpu.so maximilian_amd/ab_tabr4.so; do
-    MXG_LIB=$R/$lib timeout 300 python bench.py --workload tables --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python tools/line_fields.py "tables $lib r$round"
+    MXG_LIB=$R/$lib timeout 300 python bench.py --full --workload tables --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python tools/line_fields.py "tables $lib r$round"
   done
   for lib in maximilian_amd/libmaxigpu.so maximilian_amd/ab_pcfl0.so maximilian_amd/ab_pcfl0x.so; do
-    MXG_LIB=$R/$lib timeout 300 python bench.py --mixdown fused --no-cpu-baseline --no-extras --no-configs --steps 300 --warmup 30 2>/dev/null | python tools/line_fields.py "k1m $lib r$round"
+    MXG_LIB=$R/$lib timeout 300 python bench.py --full --mixdown fused --no-cpu-baseline --no-extras --no-configs --steps 300 --warmup 30 2>/dev/null | python tools/line_fields.py "k1m $lib r$round"
   done
-  timeout 300 python bench.py --no-cpu-baseline --no-extras --no-configs --steps 300 --warmup 30 2>/dev/null | python tools/line_fields.py "k1 r$round"
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-configs --steps 300 --warmup 30 2>/dev/null | python tools/line_fields.py "k1 r$round"
 done > $O/ab.log 2>&1; cat $O/ab.log
 cd /tmp && export TMPDIR=/tmp
 i=0

@@ -23,6 +23,6 @@ for V, N in ((1000, 512), (4099, 333), (17, 16), (40000, 512), (131072, 512)):
     print("depth 3 == depth 1:", V, N)
 PY
 for r in 1 2; do for d in 1 3; do
-timeout 300 python bench.py --workload tables --no-cpu-baseline --steps 208 --warmup 16 --kernel-events pass --verbose --tune tab_depth=$d 2>> $O/err.log | python tools/line_fields.py "tab_depth=$d r$r"
+timeout 300 python bench.py --full --workload tables --no-cpu-baseline --steps 208 --warmup 16 --kernel-events pass --verbose --tune tab_depth=$d 2>> $O/err.log | python tools/line_fields.py "tab_depth=$d r$r"
 done; done | tee $O/ab.txt
 tail -n 6 $O/t_depth.log
