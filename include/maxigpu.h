@@ -390,6 +390,35 @@ int mxg_delay_render(int mode, size_t V, size_t N, const double *d_in, const int
                      const double *d_feedback, const int32_t *d_position, double *d_mem, size_t cap,
                      int32_t *d_phase, double *d_out, void *stream);
 
+/* ---- maxiFlanger / maxiChorus banks (H:1144-1212) ------------------------------------------- */
+/* A delay line whose tap moves every sample.  ps_flags: a set bit makes that parameter [N][V] (one value per
+ * call), a clear bit [V] (the same value for the whole block).  d_delay is uint32 (the reference's unsigned
+ * delay).  Rings are VOICE-major: ring r of voice v is d_mem[(r*V + v)*cap .. +cap), zero-initialise like the
+ * ctor (C:415-417).  d_phase (int32, the rings' maxiDelayline::phase) starts at 0 (value-initialised objects).
+ * A tap size above `cap` is held to `cap` and, if d_overflow is not NULL, counted: d_overflow[v] (uint32) is
+ * INCREASED by the number of clamped taps of the call -- the one defined departure from the reference, whose
+ * ring is 705 600 slots and indexes past it there.  A size <= 0 (also NaN or beyond +-2^31, which x86 converts
+ * to INT_MIN) resets the phase on every sample, as the reference does.  Bit-exact.  d_in / d_out are [N][V]. */
+#define MXG_FX_PS_DELAY 1
+#define MXG_FX_PS_FEEDBACK 2
+#define MXG_FX_PS_SPEED 4
+#define MXG_FX_PS_DEPTH 8
+#define MXG_FX_PS_ALL 15
+/* flange(in, delay, feedback, speed, depth) (H:1166-1172): one ring; d_phase [V]; d_lfo_phase [V] double =
+ * maxiFlanger::lfo's maxiOsc::phase (the triangle, C:362-373, inc = 1./(sampleRate/speed)). */
+int mxg_flanger_render(size_t V, size_t N, const double *d_in, const uint32_t *d_delay, const double *d_feedback,
+                       const double *d_speed, const double *d_depth, int ps_flags, double *d_mem, size_t cap,
+                       int32_t *d_phase, double *d_lfo_phase, uint32_t *d_overflow, double *d_out, void *stream);
+/* chorus(in, delay, feedback, speed, depth) (H:1202-1212): two rings (dl, dl2), d_mem [2][V][cap], d_phase
+ * [2][V].  d_rand int32 [N][V]: the rand() draw voice v's lfo.noise() takes at sample n (C:214-220).  The
+ * speed enters only as lopass.lores's cutoff (resonance 1): d_coef = (c, r) from mxg_filter_coeffs_host
+ * (MXG_FLT_LORES, speed, 1.0) rows 0-1, [2][V] (coef_ps 0) or [N][2][V] (coef_ps 1).  d_lp [2][V] = the lores
+ * state x, y (maxiFilter::x, y).  ps_flags: MXG_FX_PS_DELAY / FEEDBACK / DEPTH. */
+int mxg_chorus_render(size_t V, size_t N, const double *d_in, const uint32_t *d_delay, const double *d_feedback,
+                      const double *d_depth, int ps_flags, const int32_t *d_rand, const double *d_coef, int coef_ps,
+                      double *d_mem, size_t cap, int32_t *d_phase, double *d_lp, uint32_t *d_overflow, double *d_out,
+                      void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

@@ -1801,6 +1801,132 @@ private:
     }
 };
 
+// ---- maxiFlanger (H:1144-1172), maxiChorus (H:1179-1212): one bank-of-one launch per call ---------------------------------------
+// The effects' input is nearly always another object's audio, which the engine's "same arguments as last time" prediction cannot
+// render ahead, so these two stay outside the pools: every call uploads its arguments (56 bytes), runs mxg_flanger_render /
+// mxg_chorus_render for one voice and one sample on the library's stream, and reads back the output and the overflow count.
+// The rings are the reference's 88200 * 8 doubles (H:273), allocated at the first call; a copy carries them device-to-device.
+// maxiChorus draws rand() at the call, in call order with maxiOsc::noise() and the patch's own rand() calls (C:214-220), and
+// evaluates its lores coefficients on the host libm (mxg_filter_coeffs_host).  The public `dl` / `lfo` of maxiFlanger (H:1163-1164)
+// exist so code naming them compiles; they are objects of their own and do not alias the effect's state.
+namespace maxigpu {
+namespace ps {
+template <int R>
+struct FxLine {
+    static constexpr size_t kCap = 88200 * 8;
+    // d_blk (96 bytes): in, feedback, speed, depth, c, r (f64 0..47), delay u32 @48, draw i32 @52 -- uploaded per call;
+    // out f64 @56, overflow u32 @64 -- read back; phase i32 [2] @68; lfo state f64 [2] @80 (triangle phase | lores x, y)
+    double *d_mem = nullptr;
+    unsigned char *d_blk = nullptr;
+    uint32_t ovf = 0;
+    bool init() {
+        if (dead()) return false;
+        if (d_mem) return true;
+        if (!check(mxg_init(-1), "mxg_init")) return false;
+        d_mem = static_cast<double *>(mxg_malloc(sizeof(double) * kCap * R));
+        d_blk = static_cast<unsigned char *>(mxg_malloc(96));
+        if (!d_mem || !d_blk) {
+            check(MXG_ERR_HIP, "mxg_malloc (maxiFlanger / maxiChorus ring)");
+            return false;
+        }
+        return check(mxg_memset(d_mem, 0, sizeof(double) * kCap * R, nullptr), "mxg_memset") &&  // ctor memset, C:415-417
+               check(mxg_memset(d_blk, 0, 96, nullptr), "mxg_memset") && check(mxg_sync(), "mxg_sync");
+    }
+    void release() {
+        if (d_mem) mxg_free(d_mem);
+        if (d_blk) mxg_free(d_blk);
+        d_mem = nullptr;
+        d_blk = nullptr;
+    }
+    void copy_from(const FxLine &o) {
+        ovf = o.ovf;
+        if (!o.d_mem) {
+            if (d_mem) check(mxg_memset(d_mem, 0, sizeof(double) * kCap * R, nullptr), "mxg_memset") &&
+                       check(mxg_memset(d_blk, 0, 96, nullptr), "mxg_memset");
+            return;
+        }
+        if (!init()) return;
+        check(mxg_memcpy_d2d_async(d_mem, o.d_mem, sizeof(double) * kCap * R, nullptr), "d2d ring") &&
+            check(mxg_memcpy_d2d_async(d_blk, o.d_blk, 96, nullptr), "d2d state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    // one call: a[0..5] = in, feedback, speed, depth, c, r; delay; draw
+    double run(const double *a, uint32_t delay, int32_t draw) {
+        if (!init()) return 0.0;
+        unsigned char h[56];
+        std::memcpy(h, a, 48);
+        std::memcpy(h + 48, &delay, 4);
+        std::memcpy(h + 52, &draw, 4);
+        if (!check(mxg_memcpy_h2d(d_blk, h, sizeof(h), nullptr), "h2d fx arguments")) return 0.0;
+        double *p = reinterpret_cast<double *>(d_blk);
+        const uint32_t *dly = reinterpret_cast<const uint32_t *>(d_blk + 48);
+        const int32_t *rnd = reinterpret_cast<const int32_t *>(d_blk + 52);
+        uint32_t *d_ovf = reinterpret_cast<uint32_t *>(d_blk + 64);
+        int32_t *d_phase = reinterpret_cast<int32_t *>(d_blk + 68);
+        double *d_lfo = reinterpret_cast<double *>(d_blk + 80);
+        const int st = R == 1 ? mxg_flanger_render(1, 1, p, dly, p + 1, p + 2, p + 3, 0, d_mem, kCap, d_phase, d_lfo, d_ovf, p + 7, nullptr)
+                              : mxg_chorus_render(1, 1, p, dly, p + 1, p + 3, 0, rnd, p + 4, 0, d_mem, kCap, d_phase, d_lfo, d_ovf, p + 7,
+                                                  nullptr);
+        if (!check(st, R == 1 ? "mxg_flanger_render" : "mxg_chorus_render")) return 0.0;
+        unsigned char o[12];
+        if (!check(mxg_memcpy_d2h(o, d_blk + 56, sizeof(o), nullptr), "d2h fx output")) return 0.0;
+        double out;
+        uint32_t n;
+        std::memcpy(&out, o, 8);
+        std::memcpy(&n, o + 8, 4);
+        if (n != ovf) {  // the reference indexes past memory[88200 * 8] there (undefined); the ring's end is used instead
+            complain(R == 1 ? "maxiFlanger: delay size beyond 705600 -- held to 705600" : "maxiChorus: delay size beyond 705600 -- held to 705600");
+            ovf = n;
+        }
+        return out;
+    }
+};
+}  // namespace ps
+}  // namespace maxigpu
+
+class maxiFlanger {
+    maxigpu::ps::FxLine<1> line_;
+
+public:
+    maxiFlanger() = default;
+    maxiFlanger(const maxiFlanger &o) : dl(o.dl), lfo(o.lfo) { line_.copy_from(o.line_); }
+    maxiFlanger &operator=(const maxiFlanger &o) {
+        if (this != &o) {
+            dl = o.dl;
+            lfo = o.lfo;
+            line_.copy_from(o.line_);
+        }
+        return *this;
+    }
+    ~maxiFlanger() { line_.release(); }
+    double flange(const double input, const unsigned int delay, const double feedback, const double speed, const double depth) {
+        const double a[6] = {input, feedback, speed, depth, 0.0, 0.0};
+        return line_.run(a, delay, 0);
+    }
+    maxiDelayline dl;  // H:1163-1164 (not the effect's own state, see above)
+    maxiOsc lfo;
+};
+
+class maxiChorus {
+    maxigpu::ps::FxLine<2> line_;
+
+public:
+    maxiChorus() = default;
+    maxiChorus(const maxiChorus &o) { line_.copy_from(o.line_); }
+    maxiChorus &operator=(const maxiChorus &o) {
+        if (this != &o) line_.copy_from(o.line_);
+        return *this;
+    }
+    ~maxiChorus() { line_.release(); }
+    double chorus(const double input, const unsigned int delay, const double feedback, const double speed, const double depth) {
+        const int32_t draw = std::rand();  // lfo.noise(), C:214-220
+        double coef[3] = {0.0, 0.0, 0.0};
+        const double res = 1.0;
+        maxigpu::ps::check(mxg_filter_coeffs_host(MXG_FLT_LORES, 1, &speed, &res, coef), "mxg_filter_coeffs_host");  // lores(.., speed, 1.0)
+        const double a[6] = {input, feedback, 0.0, depth, coef[0], coef[1]};
+        return line_.run(a, delay, draw);
+    }
+};
+
 // ---- maxiFFT (L/maxiFFT.h:47-110; L/maxiFFT.cpp:45-132): the hop buffer on the host, every frame on the device ---------------
 class maxiFFT {
 public:

@@ -468,6 +468,63 @@ private:
     maxigpu::DeviceArray<int32_t> pos_;
 };
 
+// ---- maxiFlanger (H:1144-1172) / maxiChorus (H:1179-1212) banks: block-rate parameters per voice --------------------------
+// (per-sample parameters: call mxg_flanger_render / mxg_chorus_render with ps_flags).  Rings voice-major, `capacity` slots each;
+// a tap above it is held there and counted in overflow() (the reference indexes past its own ring there).
+class maxiFlangerBank {
+public:
+    maxiFlangerBank(size_t voices, size_t capacity)
+        : V(voices), cap(capacity), mem_(voices * capacity), phase_(voices), lfo_(voices), ovf_(voices), delay_(voices),
+          fb_(voices), speed_(voices), depth_(voices) {}
+    void setParams(const std::vector<uint32_t> &delay, const std::vector<double> &feedback, const std::vector<double> &speed,
+                   const std::vector<double> &depth) {
+        delay_.upload(delay); fb_.upload(feedback); speed_.upload(speed); depth_.upload(depth);
+    }
+    void flange(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_flanger_render(V, N, d_in, delay_.get(), fb_.get(), speed_.get(), depth_.get(), 0, mem_.get(), cap,
+                                          phase_.get(), lfo_.get(), ovf_.get(), d_out, stream), "mxg_flanger_render");
+    }
+    uint32_t *overflow() { return ovf_.get(); }  // device [V]
+
+private:
+    size_t V, cap;
+    maxigpu::DeviceArray<double> mem_;
+    maxigpu::DeviceArray<int32_t> phase_;
+    maxigpu::DeviceArray<double> lfo_;
+    maxigpu::DeviceArray<uint32_t> ovf_, delay_;
+    maxigpu::DeviceArray<double> fb_, speed_, depth_;
+};
+
+class maxiChorusBank {
+public:
+    maxiChorusBank(size_t voices, size_t capacity)
+        : V(voices), cap(capacity), mem_(2 * voices * capacity), phase_(2 * voices), lp_(2 * voices), ovf_(voices),
+          delay_(voices), fb_(voices), depth_(voices), coef_(2 * voices) {}
+    // speed: the lores cutoff (resonance 1); its coefficients are evaluated here with the host libm
+    void setParams(const std::vector<uint32_t> &delay, const std::vector<double> &feedback, const std::vector<double> &speed,
+                   const std::vector<double> &depth) {
+        delay_.upload(delay); fb_.upload(feedback); depth_.upload(depth);
+        std::vector<double> res(V, 1.0), coef(3 * V);
+        maxigpu::check(mxg_filter_coeffs_host(MXG_FLT_LORES, V, speed.data(), res.data(), coef.data()), "mxg_filter_coeffs_host");
+        coef.resize(2 * V);
+        coef_.upload(coef);
+    }
+    // d_rand: int32 [N][V], the rand() draw each voice's lfo.noise() takes
+    void chorus(size_t N, const double *d_in, const int32_t *d_rand, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_chorus_render(V, N, d_in, delay_.get(), fb_.get(), depth_.get(), 0, d_rand, coef_.get(), 0, mem_.get(),
+                                         cap, phase_.get(), lp_.get(), ovf_.get(), d_out, stream), "mxg_chorus_render");
+    }
+    uint32_t *overflow() { return ovf_.get(); }  // device [V]
+
+private:
+    size_t V, cap;
+    maxigpu::DeviceArray<double> mem_;
+    maxigpu::DeviceArray<int32_t> phase_;
+    maxigpu::DeviceArray<double> lp_;
+    maxigpu::DeviceArray<uint32_t> ovf_, delay_;
+    maxigpu::DeviceArray<double> fb_, depth_, coef_;
+};
+
 // ---- maxiSample play family (H:602-783): V play heads over one sample ---------------------------------------
 class maxiSampleBank {
 public:

@@ -97,6 +97,11 @@ SIGNATURES = {
                                        c_void_p]),
     "mxg_delay_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mxg_flanger_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_chorus_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

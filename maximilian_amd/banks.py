@@ -679,6 +679,129 @@ class maxiDelaylineBank(_Bank):
         return self._render(1, x, size, feedback, position, out)
 
 
+FX_PS = {"delay": 1, "feedback": 2, "speed": 4, "depth": 8}  # MXG_FX_PS_* (include/maxigpu.h)
+
+
+def _fx_dev(x, dtype, what, counts):
+    """A device input of an effect bank: its element type must be `dtype`, a torch tensor must be contiguous, and its
+    element count one of `counts` -- the kernels read raw memory."""
+    want = np.dtype(dtype)
+    if isinstance(x, DeviceBuffer):
+        ok, n = x.dtype == want, int(np.prod(x.shape))
+    else:
+        ok = str(x.dtype).replace("torch.", "") == want.name and x.is_contiguous()
+        n = int(x.numel())
+    if not ok:
+        raise TypeError("%s: needs a contiguous %s device array, got %s" % (what, want.name, x.dtype))
+    if n not in counts:
+        raise ValueError("%s: %d elements, expected one of %s" % (what, n, sorted(set(counts))))
+    return n
+
+
+def _fx_param(x, V, N, dtype, what="parameter"):
+    """An effect parameter: scalar / [V] -> ([V] buffer, 0); [N][V] -> ([N][V] buffer, 1); device objects are
+    [V] unless their element count is N*V."""
+    if isinstance(x, DeviceBuffer) or hasattr(x, "data_ptr"):
+        n = _fx_dev(x, dtype, what, (V, N * V))
+        return x, int(n == N * V and N > 1)
+    a = np.asarray(x, dtype=dtype)
+    if a.ndim == 2:
+        return DeviceBuffer.from_numpy(a.reshape(N, V)), 1
+    return _as_dev(a, V, dtype), 0
+
+
+def _fx_input(x, V, N):
+    _fx_dev(x, np.float64, "input", (N * V,))
+
+
+class _FxBank(_Bank):
+    RINGS = 1
+
+    def __init__(self, voices, cap, stream=None):
+        super().__init__(voices, stream)
+        self.cap = int(cap)
+        self.memory = DeviceBuffer((self.RINGS, self.V, self.cap))  # voice-major rings, ctor memset 0 (C:415-417)
+        self.phase = DeviceBuffer((self.RINGS, self.V), np.int32)   # maxiDelayline::phase of value-initialised objects
+        self.overflow = DeviceBuffer(self.V, np.uint32)              # taps held to `cap` so far (not in the reference)
+
+    def _params(self, N, delay, feedback, depth):
+        d, pd = _fx_param(delay, self.V, N, np.uint32, "delay")
+        f, pf = _fx_param(feedback, self.V, N, np.float64, "feedback")
+        p, pp = _fx_param(depth, self.V, N, np.float64, "depth")
+        return (d, f, p), pd * FX_PS["delay"] | pf * FX_PS["feedback"] | pp * FX_PS["depth"]
+
+
+class maxiFlangerBank(_FxBank):
+    """V x maxiFlanger (H:1144-1172).  `flange(x, delay, feedback, speed, depth)` -> [N, V]; each parameter is a
+    scalar, [V] (held for the block) or [N, V] (per sample).  State: memory [1][V][cap], phase [1][V] (the delay
+    line), lfo_phase [V] (the triangle LFO), overflow [V]."""
+
+    def __init__(self, voices, cap, stream=None):
+        super().__init__(voices, cap, stream)
+        self.lfo_phase = DeviceBuffer(self.V)  # maxiOsc::phase (ctor 0, C:209-212)
+
+    def flange(self, x, delay, feedback, speed, depth, out=None):
+        N = x.shape[0]
+        (d, f, p), ps = self._params(N, delay, feedback, depth)
+        _fx_input(x, self.V, N)
+        s, pspd = _fx_param(speed, self.V, N, np.float64, "speed")
+        ps |= pspd * FX_PS["speed"]
+        out = self._out(N, out)
+        check(lib().mxg_flanger_render(self.V, N, _ptr(x), _ptr(d), _ptr(f), _ptr(s), _ptr(p), ps,
+                                       self.memory.ptr, self.cap, self.phase.ptr, self.lfo_phase.ptr,
+                                       self.overflow.ptr, _ptr(out), self.stream), "mxg_flanger_render")
+        self._keep = (d, f, s, p)
+        return out
+
+
+def chorus_coeffs(speed):
+    """(c, r) of maxiChorus's lopass.lores(noise, speed, 1.0) (C:455-468) on the host libm: [2][V] for a [V]
+    speed, [N][2][V] for an [N][V] one."""
+    sp = np.asarray(speed, np.float64)
+    flat = np.ascontiguousarray(sp.reshape(-1))
+    c = filter_coeffs(0, flat, np.ones_like(flat))[:2]
+    if sp.ndim == 2:
+        return np.ascontiguousarray(c.reshape(2, sp.shape[0], sp.shape[1]).transpose(1, 0, 2))
+    return np.ascontiguousarray(c)
+
+
+class maxiChorusBank(_FxBank):
+    """V x maxiChorus (H:1179-1212).  `chorus(x, delay, feedback, speed, depth, rand)` -> [N, V]; `rand` is the
+    int32 [N, V] rand() draw each voice's lfo.noise() takes (C:214-220).  `speed` is a scalar / [V] / [N, V]
+    (the lores cutoff; its coefficients are computed on the host), or pass `coef` ([2][V] / [N][2][V])
+    directly.  State: memory [2][V][cap], phase [2][V], lp [2][V] (lores x, y), overflow [V]."""
+    RINGS = 2
+
+    def __init__(self, voices, cap, stream=None):
+        super().__init__(voices, cap, stream)
+        self.lp = DeviceBuffer((2, self.V))  # maxiFilter::x, y (ctor 0)
+
+    def chorus(self, x, delay, feedback, speed, depth, rand, coef=None, out=None):
+        N = x.shape[0]
+        (d, f, p), ps = self._params(N, delay, feedback, depth)
+        if coef is None:
+            sp = np.asarray(speed, np.float64)
+            coef = chorus_coeffs(sp if sp.ndim == 2 else np.broadcast_to(sp, (self.V,)))
+        coef_ps = int(np.prod(coef.shape)) == 2 * N * self.V and N > 1
+        _fx_input(x, self.V, N)
+        if isinstance(coef, np.ndarray):
+            cf = DeviceBuffer.from_numpy(np.ascontiguousarray(coef, np.float64))
+        else:
+            cf = coef
+        _fx_dev(cf, np.float64, "coef", (2 * self.V, 2 * N * self.V))
+        if isinstance(rand, np.ndarray):
+            rd = DeviceBuffer.from_numpy(np.ascontiguousarray(rand, np.int32).reshape(N, self.V))
+        else:
+            rd = rand
+        _fx_dev(rd, np.int32, "rand", (N * self.V,))
+        out = self._out(N, out)
+        check(lib().mxg_chorus_render(self.V, N, _ptr(x), _ptr(d), _ptr(f), _ptr(p), ps, _ptr(rd), _ptr(cf),
+                                      int(coef_ps), self.memory.ptr, self.cap, self.phase.ptr, self.lp.ptr,
+                                      self.overflow.ptr, _ptr(out), self.stream), "mxg_chorus_render")
+        self._keep = (d, f, p, cf, rd)
+        return out
+
+
 SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAtSpeed": 4,
                 "playOnceAtSpeed": 5, "playUntilAtSpeed": 6, "play4": 7, "playAtSpeedBetweenPoints": 8,
                 # trigger-driven (mxg_sample_render_trig)
