@@ -45,6 +45,20 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rendered %zu frames x %zu channels in %.3f s; launches: osc %zu (async blocks %zu), env %zu (%zu), filter %zu\n",
                      frames, ch, secs, pool<OscPool>().launches, pool<OscPool>().async_hits, pool<EnvPool>().launches,
                      pool<EnvPool>().async_hits, pool<FilterPool>().launches);
+        // the other pools, and what the engine's machinery did (read-only counters; tests/test_gpu_dropin_fuzz.py reads this line)
+        std::fprintf(stderr, "pools: sample %zu (async blocks %zu), delay %zu (%zu), filter2 %zu (%zu), envgen %zu (%zu), filter async %zu; "
+                     "rewinds: osc %zu env %zu filter %zu sample %zu delay %zu filter2 %zu envgen %zu; "
+                     "derived blocks: osc %zu env %zu filter %zu sample %zu delay %zu filter2 %zu envgen %zu; delay undos %zu\n",
+                     pool<SamplePool>().launches, pool<SamplePool>().async_hits, pool<DelayPool>().launches, pool<DelayPool>().async_hits,
+                     pool<Filter2Pool>().launches, pool<Filter2Pool>().async_hits, pool<EnvGenPool>().launches, pool<EnvGenPool>().async_hits,
+                     pool<FilterPool>().async_hits,
+                     pool<OscPool>().rewinds, pool<EnvPool>().rewinds, pool<FilterPool>().rewinds, pool<SamplePool>().rewinds,
+                     pool<DelayPool>().rewinds, pool<Filter2Pool>().rewinds, pool<EnvGenPool>().rewinds,
+                     pool<OscPool>().derived_blocks, pool<EnvPool>().derived_blocks, pool<FilterPool>().derived_blocks,
+                     pool<SamplePool>().derived_blocks, pool<DelayPool>().derived_blocks, pool<Filter2Pool>().derived_blocks,
+                     pool<EnvGenPool>().derived_blocks, pool<DelayPool>().undos);
+        const size_t *fb = ps_form_blocks();
+        std::fprintf(stderr, "derived forms 1-9: %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", fb[1], fb[2], fb[3], fb[4], fb[5], fb[6], fb[7], fb[8], fb[9]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "dropin host: %s\n", e.what());
         return 1;

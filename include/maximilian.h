@@ -235,6 +235,8 @@ inline bool ps_derive_on() {
     static const bool on = [] { const char *e = std::getenv("MXG_PS_DERIVE"); return !(e && e[0] == '0'); }();
     return on;
 }
+// derived-argument blocks by the form that filled them (index = Hyp::form; statistics, tests)
+inline size_t *ps_form_blocks() { static size_t n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; return n; }
 inline bool ps_same_bits(double x, double y) { return !std::memcmp(&x, &y, sizeof(double)); }
 // what slot X returned (or is predicted to return) at call ordinal `ord`
 inline bool ps_out_at(const Slot &X, uint64_t ord, double &v) {
@@ -407,6 +409,7 @@ public:
         return r;
     }
     size_t launches = 0, async_hits = 0, derived_blocks = 0;  // statistics (tests)
+    size_t rewinds = 0;  // calls that missed INSIDE a cached block: the object went back to its state at that sample
 
 protected:
     // bit mask of the argument indices of `method` that may be DERIVED (predicted per sample from other objects' outputs): the ones
@@ -582,6 +585,7 @@ private:
         dv.assign(10, std::vector<double>());
         for (int k = 0; k < 10; k++) {
             if (!use[(size_t)k]) continue;
+            ps_form_blocks()[use[(size_t)k]->form % 10]++;
             dv[(size_t)k].resize(L);
             for (size_t t = 0; t < L; t++) ps_predict(*use[(size_t)k], o + t, dv[(size_t)k][t]);
         }
@@ -764,6 +768,7 @@ private:
         size_t L;
         bool rewound_at_start = false;
         if (!consumed) {  // the prediction failed inside a block: back to the state at this sample
+            rewinds++;
             if (s.pos > 0) advance(s, s.pos); else rewound_at_start = true;  // (at its first sample: the new render starts there again)
             L = 1;
         } else {
@@ -1082,6 +1087,7 @@ struct DelayPool : Pool {
     };
     unsigned derivable(int) const override { return 1u; }  // the input signal
     bool can_prefetch() const override { return false; }
+    size_t undos = 0;  // renders that first put back the cells of the block rendered last (statistics, tests)
     void enqueue(Group &G) override {
         if (G.m.size() != 1) fatal("maxiDelayline: one object per launch");  // (an engine invariant, not a user error)
         Line *ln = const_cast<Line *>(static_cast<const Line *>(G.sig[0].key));
@@ -1094,6 +1100,7 @@ struct DelayPool : Pool {
             size = size < 1 ? 1 : (int32_t)kCap;
         }
         if (G.restart && ln->saved) {  // undo the block rendered last
+            undos++;
             const size_t head = ln->saved_n - ln->saved_wrap;
             if (head) check(mxg_memcpy_d2d_async(ln->d_mem + ln->saved_first, ln->d_save, sizeof(double) * head, stream), "d2d restore");
             if (ln->saved_wrap) check(mxg_memcpy_d2d_async(ln->d_mem, ln->d_save + head, sizeof(double) * ln->saved_wrap, stream), "d2d restore");
