@@ -419,6 +419,53 @@ int mxg_chorus_render(size_t V, size_t N, const double *d_in, const uint32_t *d_
                       double *d_mem, size_t cap, int32_t *d_phase, double *d_lp, uint32_t *d_overflow, double *d_out,
                       void *stream);
 
+/* ---- maxiDynamics / maxiRMS (H:2579-2897, K12) ----------------------------------------------
+ * A bank of V compressor / expander / companders.  d_sig, d_control, d_out (and d_level_db, optional: the detector
+ * level in dB each sample was compared with) are [N][V]; d_sig == d_control is compress() and is read once.  The six
+ * parameters of maxiDynamics::play are [V], or [N][V] where their MXG_DYN_PS_* bit is set in ps_flags.  Per voice,
+ * [V]: d_window (RMS window, samples), d_lookahead (samples; 0 = off), d_analyser (MXG_DYN_PEAK / MXG_DYN_RMS).
+ * d_stages_high / d_stages_low: the [nstages][6] tables (mxg_envgen_stages_host, mxg_envgen_set_time_host) of
+ * arEnvHigh / arEnvLow, one shape each per bank; the reference's are setupASR(10, 10), retrigger and loop off.
+ * Carried state: d_rms_ring [cap_rms][V] and d_la_ring [cap_la][V] (slot-major; the reference's hold 500 ms and 1 s of
+ * samples), d_rms_pos / d_la_pos int32 [V] (maxiRingBuf::idx; a stored position outside the ring restarts at slot 0),
+ * d_running [V] (maxiRMS::runningRMS), and the envelopes' d_dst_* [5][V] / d_ist_* [7][V] exactly as
+ * mxg_envgen_render keeps them (a fresh envelope: previousValue = 1 and firstTrigger = 1 for the three detectors,
+ * everything else 0).  A window above cap_rms or a look-ahead above cap_la is held at the capacity and d_overflow [V]
+ * (optional) is INCREASED by one per such parameter per call: the one defined departure from the reference.
+ * Reproduces what the reference computes: outDB starts as log10(sig) * 20, so a sample with sig <= 0 that no section
+ * overwrites gives exactly 0.0 and does NOT push the look-ahead ring; the scale is control / outAmp.
+ * Bit-exact: the rings, positions, runningRMS, envelope states, overflow counts and the positions of NaN and exact
+ * 0.0 in d_out -- as long as no detector level lies within the device log10's error (~1e-13 dB) of a boundary it is
+ * compared with.  Tolerance: the non-zero values of d_out (device log10 and pow), d_level_db. */
+#define MXG_DYN_PEAK 0
+#define MXG_DYN_RMS 1
+#define MXG_DYN_PS_THRESHOLD_HIGH 1
+#define MXG_DYN_PS_RATIO_HIGH 2
+#define MXG_DYN_PS_KNEE_HIGH 4
+#define MXG_DYN_PS_THRESHOLD_LOW 8
+#define MXG_DYN_PS_RATIO_LOW 16
+#define MXG_DYN_PS_KNEE_LOW 32
+#define MXG_DYN_PS_ALL 63
+int mxg_dynamics_render(size_t V, size_t N, const double *d_sig, const double *d_control, const double *d_threshold_high,
+                        const double *d_ratio_high, const double *d_knee_high, const double *d_threshold_low,
+                        const double *d_ratio_low, const double *d_knee_low, int ps_flags, const uint32_t *d_window,
+                        const uint32_t *d_lookahead, const int32_t *d_analyser, const double *d_stages_high,
+                        const double *d_stages_low, int nstages, double *d_rms_ring, size_t cap_rms, double *d_la_ring,
+                        size_t cap_la, int32_t *d_rms_pos, int32_t *d_la_pos, double *d_running, double *d_dst_high,
+                        int64_t *d_ist_high, double *d_dst_low, int64_t *d_ist_low, uint32_t *d_overflow, double *d_out,
+                        double *d_level_db, void *stream);
+/* maxiRMS::play (H:2604-2610) alone, from the same code: d_ring [cap][V], d_pos [V], d_running [V], d_window [V]
+ * (samples; above cap: held there and counted in d_overflow).  Bit-exact (the square root is correctly rounded). */
+int mxg_rms_render(size_t V, size_t N, const double *d_in, const uint32_t *d_window, double *d_ring, size_t cap,
+                   int32_t *d_pos, double *d_running, uint32_t *d_overflow, double *d_out, void *stream);
+/* maxiEnvGen::setTime(index, ms) (H:2449-2462, setupSegmentTime H:2532-2546) on row `index` of a HOST [nstages][6]
+ * table: length = floor(ms / 1000 * sampleRate), gradient = 1 / length, or a HOLD stage for ms == -46692.  Returns 0, or
+ * 1 where setTime reports an error (a second HOLD stage; an index past the table, which the reference lets through
+ * for index == nstages and then writes outside its vector).  Whether a HOLD stage exists is read off the table.
+ * maxiDynamics::setAttackHigh / setReleaseHigh / setAttackLow / setReleaseLow are setupASR(10, 10) once, then
+ * setTime(0, ms) / setTime(2, ms).  Host arithmetic only: bit-exact. */
+int mxg_envgen_set_time_host(double *h_stages, size_t nstages, size_t index, double ms);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

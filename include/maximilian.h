@@ -2292,6 +2292,18 @@ public:
     void setupADSR(const double attack, const double decay, const double sustain, const double release) {
         setup({0, 1, sustain, sustain, 0}, {attack, decay, maxiEnvGen::HOLD, release}, {1, 1, 1, 1}, false, false);
     }
+    bool setTime(size_t index, double value) {  // H:2449-2462: one stage's length (ms, or HOLD); returns the reference's `error`
+        MAXIGPU_TRY {
+        if (!shape_.d_stages || shape_.nstages <= 0) return 1;  // (no stages: the reference indexes an empty vector)
+        pool().settle(slot_);
+        std::vector<double> tab(6 * static_cast<size_t>(shape_.nstages));
+        if (!maxigpu::ps::check(mxg_memcpy_d2h(tab.data(), shape_.d_stages, sizeof(double) * tab.size(), nullptr), "d2h stages")) return 1;
+        if (mxg_envgen_set_time_host(tab.data(), static_cast<size_t>(shape_.nstages), index, value) != 0) return 1;
+        maxigpu::ps::check(mxg_memcpy_h2d(shape_.d_stages, tab.data(), sizeof(double) * tab.size(), nullptr), "h2d stages");
+        return 0;
+        }
+        MAXIGPU_CATCH(return true)
+    }
     void setRetrigger(const bool val) { pool().settle(slot_); shape_.retrigger = val; }
     bool getRetrigger() { return shape_.retrigger; }
     void setLoop(const bool val) { pool().settle(slot_); shape_.loop = val; }
@@ -2317,6 +2329,271 @@ private:
         }
         MAXIGPU_CATCH(return)
     }
+};
+
+// ---- maxiRingBuf (H:424-494): a host value type, no device work --------------------------------------------------------------
+class maxiRingBuf {
+public:
+    maxiRingBuf() {}
+    void setup(size_t N) { buf.assign(N, 0.0); }  // H:429-432 (idx stays where it is, as in the reference)
+    void push(double x) {                         // H:434-440
+        buf[idx] = x;
+        idx++;
+        if (idx == buf.size()) idx = 0;
+    }
+    size_t size() { return buf.size(); }
+    double head() { return idx == 0 ? buf[buf.size() - 1] : buf[idx - 1]; }  // H:446
+    double tail(size_t N) { return idx >= N ? buf[idx - N] : buf[buf.size() - (N - idx)]; }  // H:449-458
+    using reduceFunction = std::function<double(double, double)>;
+    double reduce(size_t N, reduceFunction func, double initval) {  // H:470-487 (initval is unused there too)
+        (void)initval;
+        double val = 0;
+        if (idx >= N) {
+            for (size_t i = idx - N; i < idx; i++) val = func(val, buf[i]);
+        } else {
+            for (size_t i = buf.size() - (N - idx); i < buf.size(); i++) val = func(val, buf[i]);
+            for (size_t i = 0; i < idx; i++) val = func(val, buf[i]);
+        }
+        return val;
+    }
+
+private:
+    std::vector<double> buf;
+    size_t idx = 0;
+};
+
+// ---- maxiRMS (H:2579-2616), maxiDynamics (H:2625-2897): one bank-of-one launch per call ----------------------------------------
+// Like maxiFlanger their input is another object's audio, so they stay outside the prediction pools: every call uploads its
+// arguments, runs mxg_rms_render / mxg_dynamics_render for one voice and one sample on the library's stream and reads the output
+// back.  The rings are allocated at the first call, in the sizes the reference's constructor gives them from the sample rate in
+// force when the object was CONSTRUCTED (500 ms and 1 s of samples); a copy carries rings and state device-to-device.
+namespace maxigpu {
+namespace ps {
+inline size_t ms_to_samps(double ms) { return static_cast<size_t>(ms / 1000.0 * maxiSettings::sampleRate); }  // H:944-947
+inline double samps_to_ms(size_t samples) { return samples / maxiSettings::sampleRate * 1000.0; }             // H:949-952: an integer division
+
+struct RmsLine {
+    // d_blk (48 bytes): in f64 @0, window u32 @8 -- uploaded per call; out f64 @16, overflow u32 @24 -- read back; pos i32 @28; running f64 @32
+    double *d_ring = nullptr;
+    unsigned char *d_blk = nullptr;
+    size_t cap = 0, window = 0;
+    bool zero_running = false;
+    void release() {
+        if (d_ring) mxg_free(d_ring);
+        if (d_blk) mxg_free(d_blk);
+        d_ring = nullptr;
+        d_blk = nullptr;
+    }
+    bool alloc(size_t n) {  // a new zeroed ring (maxiRingBuf::setup); position and running sum stay (the reference keeps idx too)
+        if (dead() || n == 0 || !check(mxg_init(-1), "mxg_init")) return false;
+        if (d_ring) mxg_free(d_ring);
+        d_ring = static_cast<double *>(mxg_malloc(sizeof(double) * n));
+        const bool fresh = !d_blk;
+        if (fresh) d_blk = static_cast<unsigned char *>(mxg_malloc(48));
+        if (!d_ring || !d_blk) {
+            check(MXG_ERR_HIP, "mxg_malloc (maxiRMS ring)");
+            return false;
+        }
+        cap = n;
+        return check(mxg_memset(d_ring, 0, sizeof(double) * n, nullptr), "mxg_memset") &&
+               (!fresh || check(mxg_memset(d_blk, 0, 48, nullptr), "mxg_memset")) && check(mxg_sync(), "mxg_sync");
+    }
+    void copy_from(const RmsLine &o) {
+        release();
+        cap = o.cap;
+        window = o.window;
+        zero_running = o.zero_running;
+        if (!o.d_ring || !alloc(o.cap)) return;
+        check(mxg_memcpy_d2d_async(d_ring, o.d_ring, sizeof(double) * cap, nullptr), "d2d ring") &&
+            check(mxg_memcpy_d2d_async(d_blk, o.d_blk, 48, nullptr), "d2d state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    double run(double x) {
+        if (!d_ring || dead()) return 0.0;
+        if (zero_running) {
+            const double z = 0.0;
+            if (!check(mxg_memcpy_h2d(d_blk + 32, &z, 8, nullptr), "h2d runningRMS")) return 0.0;
+            zero_running = false;
+        }
+        unsigned char h[16] = {0};
+        const uint32_t w = static_cast<uint32_t>(window);
+        std::memcpy(h, &x, 8);
+        std::memcpy(h + 8, &w, 4);
+        if (!check(mxg_memcpy_h2d(d_blk, h, sizeof(h), nullptr), "h2d rms arguments")) return 0.0;
+        const int st = mxg_rms_render(1, 1, reinterpret_cast<double *>(d_blk), reinterpret_cast<uint32_t *>(d_blk + 8), d_ring, cap,
+                                      reinterpret_cast<int32_t *>(d_blk + 28), reinterpret_cast<double *>(d_blk + 32),
+                                      reinterpret_cast<uint32_t *>(d_blk + 24), reinterpret_cast<double *>(d_blk + 16), nullptr);
+        if (!check(st, "mxg_rms_render")) return 0.0;
+        double out = 0.0;
+        if (!check(mxg_memcpy_d2h(&out, d_blk + 16, 8, nullptr), "d2h rms output")) return 0.0;
+        return out;
+    }
+};
+
+struct DynLine {
+    // d_blk (592 bytes).  Uploaded per call, @0..367: sig, control, thresholdHigh, ratioHigh, kneeHigh, thresholdLow, ratioLow, kneeLow
+    // (f64 @0..63), window u32 @64, lookahead u32 @68, analyser i32 @72, the stage tables of arEnvHigh @80 and arEnvLow @224 ([3][6] f64).
+    // Read back: out f64 @368, overflow u32 @376.  State: rms pos i32 @384, look-ahead pos i32 @388, runningRMS f64 @392, the
+    // envelopes' [5] doubles @400 / @440 and [7] int64 @480 / @536 (mxg_envgen_render's arrays for one voice).
+    static constexpr size_t kBlk = 592, kArgs = 368;
+    double *d_rms = nullptr, *d_la = nullptr;
+    unsigned char *d_blk = nullptr;
+    size_t cap_rms = 0, cap_la = 0;  // from the sample rate at construction
+    uint32_t window = 0, look = 0;
+    int32_t analyser = MXG_DYN_RMS;
+    double tab_h[18], tab_l[18];
+    bool zero_running = false;
+    void construct() {  // maxiDynamics() H:2631-2652
+        cap_rms = ms_to_samps(500);
+        cap_la = maxiSettings::sampleRate * 1;
+        const size_t w = ms_to_samps(50);  // rms.setup(500, 50)
+        window = w <= cap_rms ? static_cast<uint32_t>(w) : 0;
+        const double levels[4] = {0, 1, 1, 0}, times[3] = {10, -46692.0, 10}, curves[3] = {1, 1, 1};  // setupASR(10, 10)
+        mxg_envgen_stages_host(4, levels, times, curves, tab_h);
+        std::memcpy(tab_l, tab_h, sizeof(tab_h));
+    }
+    bool init() {
+        if (dead()) return false;
+        if (d_blk) return true;
+        if (cap_rms == 0 || cap_la == 0) return false;
+        if (!check(mxg_init(-1), "mxg_init")) return false;
+        d_rms = static_cast<double *>(mxg_malloc(sizeof(double) * cap_rms));
+        d_la = static_cast<double *>(mxg_malloc(sizeof(double) * cap_la));
+        d_blk = static_cast<unsigned char *>(mxg_malloc(kBlk));
+        if (!d_rms || !d_la || !d_blk) {
+            check(MXG_ERR_HIP, "mxg_malloc (maxiDynamics rings)");
+            return false;
+        }
+        unsigned char h[kBlk] = {0};
+        const double one = 1.0;
+        const int64_t ione = 1;
+        for (int e = 0; e < 2; e++) {  // fresh maxiTrigger detectors: previousValue = 1, firstTrigger = 1 (H:593-594)
+            for (int k = 2; k < 5; k++) std::memcpy(h + 400 + 40 * e + 8 * k, &one, 8);
+            for (int k = 4; k < 7; k++) std::memcpy(h + 480 + 56 * e + 8 * k, &ione, 8);
+        }
+        return check(mxg_memset(d_rms, 0, sizeof(double) * cap_rms, nullptr), "mxg_memset") &&
+               check(mxg_memset(d_la, 0, sizeof(double) * cap_la, nullptr), "mxg_memset") &&
+               check(mxg_memcpy_h2d(d_blk, h, kBlk, nullptr), "h2d maxiDynamics state") && check(mxg_sync(), "mxg_sync");
+    }
+    void release() {
+        if (d_rms) mxg_free(d_rms);
+        if (d_la) mxg_free(d_la);
+        if (d_blk) mxg_free(d_blk);
+        d_rms = d_la = nullptr;
+        d_blk = nullptr;
+    }
+    void copy_from(const DynLine &o) {
+        release();
+        cap_rms = o.cap_rms; cap_la = o.cap_la; window = o.window; look = o.look; analyser = o.analyser; zero_running = o.zero_running;
+        std::memcpy(tab_h, o.tab_h, sizeof(tab_h));
+        std::memcpy(tab_l, o.tab_l, sizeof(tab_l));
+        if (!o.d_blk || !init()) return;
+        check(mxg_memcpy_d2d_async(d_rms, o.d_rms, sizeof(double) * cap_rms, nullptr), "d2d ring") &&
+            check(mxg_memcpy_d2d_async(d_la, o.d_la, sizeof(double) * cap_la, nullptr), "d2d ring") &&
+            check(mxg_memcpy_d2d_async(d_blk, o.d_blk, kBlk, nullptr), "d2d state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    double run(const double (&a)[8]) {
+        if (!init()) return 0.0;
+        if (zero_running) {  // maxiRMS::setWindowSize zeroes the running sum, not the ring (H:2590-2596)
+            const double z = 0.0;
+            if (!check(mxg_memcpy_h2d(d_blk + 392, &z, 8, nullptr), "h2d runningRMS")) return 0.0;
+            zero_running = false;
+        }
+        unsigned char h[kArgs] = {0};
+        std::memcpy(h, a, 64);
+        std::memcpy(h + 64, &window, 4);
+        std::memcpy(h + 68, &look, 4);
+        std::memcpy(h + 72, &analyser, 4);
+        std::memcpy(h + 80, tab_h, 144);
+        std::memcpy(h + 224, tab_l, 144);
+        if (!check(mxg_memcpy_h2d(d_blk, h, kArgs, nullptr), "h2d maxiDynamics arguments")) return 0.0;
+        double *p = reinterpret_cast<double *>(d_blk);
+        const int st = mxg_dynamics_render(
+            1, 1, p, p + 1, p + 2, p + 3, p + 4, p + 5, p + 6, p + 7, 0, reinterpret_cast<uint32_t *>(d_blk + 64),
+            reinterpret_cast<uint32_t *>(d_blk + 68), reinterpret_cast<int32_t *>(d_blk + 72), p + 10, p + 28, 3, d_rms, cap_rms, d_la, cap_la,
+            reinterpret_cast<int32_t *>(d_blk + 384), reinterpret_cast<int32_t *>(d_blk + 388), p + 49, p + 50,
+            reinterpret_cast<int64_t *>(d_blk + 480), p + 55, reinterpret_cast<int64_t *>(d_blk + 536),
+            reinterpret_cast<uint32_t *>(d_blk + 376), p + 46, nullptr, nullptr);
+        if (!check(st, "mxg_dynamics_render")) return 0.0;
+        double out = 0.0;
+        if (!check(mxg_memcpy_d2h(&out, d_blk + 368, 8, nullptr), "d2h maxiDynamics output")) return 0.0;
+        return out;
+    }
+};
+}  // namespace ps
+}  // namespace maxigpu
+
+class maxiRMS {
+    maxigpu::ps::RmsLine line_;
+
+public:
+    maxiRMS() {}
+    maxiRMS(const maxiRMS &o) { line_.copy_from(o.line_); }
+    maxiRMS &operator=(const maxiRMS &o) {
+        if (this != &o) line_.copy_from(o.line_);
+        return *this;
+    }
+    ~maxiRMS() { line_.release(); }
+    void setup(double maxLength, double windowSize) {  // H:2584-2587
+        if (!line_.alloc(maxigpu::ps::ms_to_samps(maxLength))) line_.cap = 0;
+        setWindowSize(windowSize);
+    }
+    void setWindowSize(double newWindowSize) {  // H:2590-2596
+        const size_t n = maxigpu::ps::ms_to_samps(newWindowSize);
+        if (n <= line_.cap) line_.window = n;
+        line_.zero_running = true;
+    }
+    double getWindowSize() { return maxigpu::ps::samps_to_ms(line_.window); }
+    double play(double signal) {  // H:2604-2610
+        if (!line_.d_ring) {  // no buffer: the reference writes through an empty vector here
+            maxigpu::ps::complain("maxiRMS::play before setup() -- silence");
+            return 0.0;
+        }
+        return line_.run(signal);
+    }
+};
+
+class maxiDynamics {
+    maxigpu::ps::DynLine line_;
+
+public:
+    enum ANALYSERS { PEAK, RMS };
+    maxiDynamics() { line_.construct(); }
+    maxiDynamics(const maxiDynamics &o) { line_.copy_from(o.line_); }
+    maxiDynamics &operator=(const maxiDynamics &o) {
+        if (this != &o) line_.copy_from(o.line_);
+        return *this;
+    }
+    ~maxiDynamics() { line_.release(); }
+    double play(double sig, double control, double thresholdHigh, double ratioHigh, double kneeHigh, double thresholdLow, double ratioLow,
+                double kneeLow) {  // H:2668-2761
+        const double a[8] = {sig, control, thresholdHigh, ratioHigh, kneeHigh, thresholdLow, ratioLow, kneeLow};
+        return line_.run(a);
+    }
+    double compress(double sig, double threshold, double ratio, double knee) { return play(sig, sig, threshold, ratio, knee, 0, 0, 0); }
+    double sidechainCompress(double sig, double control, double threshold, double ratio, double knee) {
+        return play(sig, control, threshold, ratio, knee, 0, 0, 0);
+    }
+    double compandAbove(double sig, double control, double threshold, double ratio, double knee) {
+        return play(sig, control, threshold, ratio, knee, 0, 0, 0);
+    }
+    double compandBelow(double sig, double control, double threshold, double ratio, double knee) {
+        return play(sig, control, 0, 0, 0, threshold, ratio, knee);
+    }
+    void setAttackHigh(double attack) { mxg_envgen_set_time_host(line_.tab_h, 3, 0, attack); }     // arEnvHigh.setTime(0, attack)
+    void setReleaseHigh(double release) { mxg_envgen_set_time_host(line_.tab_h, 3, 2, release); }  // arEnvHigh.setTime(2, release)
+    void setAttackLow(double attack) { mxg_envgen_set_time_host(line_.tab_l, 3, 0, attack); }
+    void setReleaseLow(double release) { mxg_envgen_set_time_host(line_.tab_l, 3, 2, release); }
+    void setLookAhead(double length) {  // H:2844-2847
+        const size_t n = maxigpu::ps::ms_to_samps(length);
+        line_.look = static_cast<uint32_t>(n < line_.cap_la ? n : line_.cap_la);
+    }
+    double getLookAhead() { return maxigpu::ps::samps_to_ms(line_.look); }
+    void setRMSWindowSize(double winSize) {  // H:2859-2861 over maxiRMS::setWindowSize
+        const size_t n = maxigpu::ps::ms_to_samps(500.0 < winSize ? 500.0 : winSize);  // std::min(winSize, 500.0)
+        if (n <= line_.cap_rms) line_.window = static_cast<uint32_t>(n);
+        line_.zero_running = true;
+    }
+    void setInputAnalyser(ANALYSERS mode) { line_.analyser = mode == PEAK ? MXG_DYN_PEAK : MXG_DYN_RMS; }
 };
 
 // ---- maxiIFFT (L/maxiFFT.h:117-156; L/maxiFFT.cpp:141-192): one inverse transform per hop on the device -------------------------

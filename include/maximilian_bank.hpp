@@ -18,6 +18,7 @@
 // per callback buffer.  Every method that can fail throws std::runtime_error carrying
 // mxg_last_error(); nothing here falls back to the CPU.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -523,6 +524,125 @@ private:
     maxigpu::DeviceArray<double> lp_;
     maxigpu::DeviceArray<uint32_t> ovf_, delay_;
     maxigpu::DeviceArray<double> fb_, depth_, coef_;
+};
+
+// ---- maxiDynamics (H:2625-2897) / maxiRMS (H:2579-2616) banks (K12): block-rate parameters per voice ------------------------
+// (per-sample parameters: call mxg_dynamics_render with ps_flags).  Rings slot-major, [capacity][V]; the defaults are the
+// reference's (500 ms and 1 s of samples at the sample rate in force at construction).  Times in ms as in the reference; the four
+// attack / release times are one value per bank.
+class maxiDynamicsBank {
+public:
+    enum ANALYSERS { PEAK = MXG_DYN_PEAK, RMS = MXG_DYN_RMS };
+    explicit maxiDynamicsBank(size_t voices, size_t capRms = 0, size_t capLookahead = 0)
+        : V(voices), capR(capRms ? capRms : msToSamps(500)), capL(capLookahead ? capLookahead : mxg_sample_rate()), rring_(voices * capR),
+          lring_(voices * capL), rpos_(voices), lpos_(voices), running_(voices), dstH_(5 * voices), dstL_(5 * voices), istH_(7 * voices),
+          istL_(7 * voices), ovf_(voices), win_(voices), look_(voices), an_(voices), tabH_(18), tabL_(18), window(voices, 0),
+          lookahead(voices, 0), analyser(voices, RMS) {
+        for (int e = 0; e < 2; e++) {  // fresh envelopes: previousValue = 1, firstTrigger = 1 for the three detectors (H:593-594)
+            std::vector<double> d(5 * V, 0.0);
+            std::vector<int64_t> i(7 * V, 0);
+            std::fill(d.begin() + 2 * V, d.end(), 1.0);
+            std::fill(i.begin() + 4 * V, i.end(), 1);
+            (e ? dstL_ : dstH_).upload(d);
+            (e ? istL_ : istH_).upload(i);
+        }
+        const double levels[4] = {0, 1, 1, 0}, times[3] = {10, -46692.0, 10}, curves[3] = {1, 1, 1};  // setupASR(10, 10)
+        stagesHigh.assign(18, 0.0);
+        maxigpu::check(mxg_envgen_stages_host(4, levels, times, curves, stagesHigh.data()), "mxg_envgen_stages_host");
+        stagesLow = stagesHigh;
+        const size_t w = msToSamps(50);  // rms.setup(500, 50)
+        if (w <= capR) std::fill(window.begin(), window.end(), (uint32_t)w);
+    }
+    static size_t msToSamps(double ms) { return static_cast<size_t>(ms / 1000.0 * mxg_sample_rate()); }  // H:944-947
+    void setAttackHigh(double ms) { setTime(stagesHigh, 0, ms); }
+    void setReleaseHigh(double ms) { setTime(stagesHigh, 2, ms); }
+    void setAttackLow(double ms) { setTime(stagesLow, 0, ms); }
+    void setReleaseLow(double ms) { setTime(stagesLow, 2, ms); }
+    void setLookAhead(double ms) {  // H:2844-2847, every voice
+        const size_t n = msToSamps(ms);
+        std::fill(lookahead.begin(), lookahead.end(), (uint32_t)(n < capL ? n : capL));
+        dirty_ = true;
+    }
+    void setRMSWindowSize(double ms) {  // H:2859-2861, every voice: a request above the ring is ignored, the running sum is zeroed
+        const size_t n = msToSamps(500.0 < ms ? 500.0 : ms);
+        if (n <= capR) std::fill(window.begin(), window.end(), (uint32_t)n);
+        running_.upload(std::vector<double>(V, 0.0));
+        dirty_ = true;
+    }
+    void setInputAnalyser(ANALYSERS mode) {
+        std::fill(analyser.begin(), analyser.end(), (int32_t)mode);
+        dirty_ = true;
+    }
+    void setParams(const std::vector<double> &thresholdHigh, const std::vector<double> &ratioHigh, const std::vector<double> &kneeHigh,
+                   const std::vector<double> &thresholdLow, const std::vector<double> &ratioLow, const std::vector<double> &kneeLow) {
+        p_[0].upload(thresholdHigh); p_[1].upload(ratioHigh); p_[2].upload(kneeHigh);
+        p_[3].upload(thresholdLow); p_[4].upload(ratioLow); p_[5].upload(kneeLow);
+    }
+    // compress(): the high section only, the signal is its own side chain
+    void setCompress(const std::vector<double> &threshold, const std::vector<double> &ratio, const std::vector<double> &knee) {
+        const std::vector<double> z(V, 0.0);
+        setParams(threshold, ratio, knee, z, z, z);
+    }
+    // play(): d_control may be d_sig.  d_level_db (optional, [N][V]): the detector level in dB.
+    void play(size_t N, const double *d_sig, const double *d_control, double *d_out, double *d_level_db = nullptr, void *stream = nullptr) {
+        if (dirty_) {
+            win_.upload(window); look_.upload(lookahead); an_.upload(analyser); tabH_.upload(stagesHigh); tabL_.upload(stagesLow);
+            dirty_ = false;
+        }
+        maxigpu::check(mxg_dynamics_render(V, N, d_sig, d_control, p_[0].get(), p_[1].get(), p_[2].get(), p_[3].get(), p_[4].get(),
+                                           p_[5].get(), 0, win_.get(), look_.get(), an_.get(), tabH_.get(), tabL_.get(), 3, rring_.get(),
+                                           capR, lring_.get(), capL, rpos_.get(), lpos_.get(), running_.get(), dstH_.get(), istH_.get(),
+                                           dstL_.get(), istL_.get(), ovf_.get(), d_out, d_level_db, stream), "mxg_dynamics_render");
+    }
+    void compress(size_t N, const double *d_sig, double *d_out, void *stream = nullptr) { play(N, d_sig, d_sig, d_out, nullptr, stream); }
+    uint32_t *overflow() { return ovf_.get(); }  // device [V]
+    size_t capacityRms() const { return capR; }
+    size_t capacityLookahead() const { return capL; }
+
+private:
+    void setTime(std::vector<double> &tab, size_t index, double ms) {
+        maxigpu::check(mxg_envgen_set_time_host(tab.data(), 3, index, ms), "mxg_envgen_set_time_host");
+        dirty_ = true;
+    }
+    size_t V, capR, capL;
+    maxigpu::DeviceArray<double> rring_, lring_;
+    maxigpu::DeviceArray<int32_t> rpos_, lpos_;
+    maxigpu::DeviceArray<double> running_, dstH_, dstL_;
+    maxigpu::DeviceArray<int64_t> istH_, istL_;
+    maxigpu::DeviceArray<uint32_t> ovf_, win_, look_;
+    maxigpu::DeviceArray<int32_t> an_;
+    maxigpu::DeviceArray<double> tabH_, tabL_, p_[6];
+    bool dirty_ = true;
+
+public:
+    // host copies, in samples / per voice: edit and call touch() for per-voice settings
+    std::vector<uint32_t> window, lookahead;
+    std::vector<int32_t> analyser;
+    std::vector<double> stagesHigh, stagesLow;  // [3][6]
+    void touch() { dirty_ = true; }
+};
+
+class maxiRMSBank {
+public:
+    maxiRMSBank(size_t voices, size_t capacity)
+        : V(voices), cap(capacity), ring_(voices * capacity), pos_(voices), running_(voices), ovf_(voices), win_(voices) {}
+    void setWindowSize(double ms) {  // H:2590-2596, every voice
+        const size_t n = maxiDynamicsBank::msToSamps(ms);
+        if (n <= cap) win_.upload(std::vector<uint32_t>(V, (uint32_t)n));
+        running_.upload(std::vector<double>(V, 0.0));
+    }
+    void play(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_rms_render(V, N, d_in, win_.get(), ring_.get(), cap, pos_.get(), running_.get(), ovf_.get(), d_out, stream),
+                       "mxg_rms_render");
+    }
+    uint32_t *overflow() { return ovf_.get(); }
+
+private:
+    size_t V, cap;
+    maxigpu::DeviceArray<double> ring_;
+    maxigpu::DeviceArray<int32_t> pos_;
+    maxigpu::DeviceArray<double> running_;
+    maxigpu::DeviceArray<uint32_t> ovf_, win_;
 };
 
 // ---- maxiSample play family (H:602-783): V play heads over one sample ---------------------------------------

@@ -102,6 +102,11 @@ SIGNATURES = {
     "mxg_chorus_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "mxg_dynamics_render": (c_int, [c_size_t, c_size_t] + [c_void_p] * 8 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_size_t,
+                                                                                                       c_void_p, c_size_t] + [c_void_p] * 11),
+    "mxg_rms_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "mxg_envgen_set_time_host": (c_int, [c_void_p, c_size_t, c_size_t, c_double]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

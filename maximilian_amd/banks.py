@@ -802,6 +802,213 @@ class maxiChorusBank(_FxBank):
         return out
 
 
+DYN_PS = {"thresholdHigh": 1, "ratioHigh": 2, "kneeHigh": 4, "thresholdLow": 8, "ratioLow": 16, "kneeLow": 32}  # MXG_DYN_PS_*
+
+
+def ms_to_samps(ms):
+    """maxiConvert::msToSamps (H:944-947): truncation to size_t."""
+    return int(float(ms) / 1000.0 * maxiSettings.sampleRate)
+
+
+class _DynControl:
+    """The host side of maxiDynamics (H:2625-2897): what its constructor and setters leave behind, as the arrays
+    mxg_dynamics_render reads.  Per voice: window / lookahead (samples) and analyser; per bank: the two setupASR(10, 10)
+    stage tables.  No device work here (tests/dyn_host.py drives the host build of the kernel's arithmetic with it)."""
+    PEAK, RMS = 0, 1
+
+    def _init_control(self, V, cap_rms, cap_lookahead):
+        self.V = int(V)
+        # both rings are sized from the sample rate in force at construction (H:2637, H:2651)
+        self.cap_rms = int(cap_rms) if cap_rms is not None else ms_to_samps(500)
+        self.cap_lookahead = int(cap_lookahead) if cap_lookahead is not None else int(maxiSettings.sampleRate)
+        self.window = np.zeros(self.V, np.uint32)       # maxiRMS::windowSize = 0 until setup()
+        self.lookahead = np.zeros(self.V, np.uint32)    # lookAheadSize = 0
+        self.analyser = np.full(self.V, self.RMS, np.int32)
+        self._zero_running = np.zeros(self.V, bool)
+        self._set_window(50.0)                          # rms.setup(500, 50)
+        self._zero_running[:] = False
+        self.stages_high, self.stages_low = self._asr(), self._asr()
+        self._dirty = True
+
+    @staticmethod
+    def _asr():
+        levels, times, curves = np.array([0.0, 1, 1, 0]), np.array([10.0, -46692.0, 10.0]), np.ones(3)
+        st = np.zeros((3, 6))
+        check(lib().mxg_envgen_stages_host(4, levels.ctypes.data, times.ctypes.data, curves.ctypes.data, st.ctypes.data),
+              "mxg_envgen_stages_host")
+        return st
+
+    def _select(self, x, voices, dtype=np.float64):
+        """(indices, values) of a setter call made on `voices` (None = every voice) with a scalar or one value per voice."""
+        idx = np.arange(self.V)[slice(None) if voices is None else voices].reshape(-1)
+        a = np.asarray(x, dtype)
+        if a.ndim and a.shape != idx.shape:
+            raise ValueError("expected a scalar or %d values, got shape %s" % (idx.size, a.shape))
+        return idx, np.broadcast_to(a, idx.shape)
+
+    def _set_time(self, table, index, ms):
+        check(lib().mxg_envgen_set_time_host(table.ctypes.data, table.shape[0], index, float(ms)), "mxg_envgen_set_time_host")
+        self._dirty = True
+
+    def invalidate(self):
+        """Call after editing window / lookahead / analyser / stages_high / stages_low in place (all host arrays, in samples)."""
+        self._dirty = True
+
+    def setAttackHigh(self, attack): self._set_time(self.stages_high, 0, attack)    # H:2815-2817
+    def setReleaseHigh(self, release): self._set_time(self.stages_high, 2, release)  # H:2822-2824
+    def setAttackLow(self, attack): self._set_time(self.stages_low, 0, attack)      # H:2829-2831
+    def setReleaseLow(self, release): self._set_time(self.stages_low, 2, release)    # H:2836-2838
+
+    def setLookAhead(self, length, voices=None):
+        """H:2844-2847: msToSamps, held at the ring's size.  Scalar or one value per voice of `voices` (None = all)."""
+        idx, ms = self._select(length, voices)
+        for v, m in zip(idx.tolist(), ms.tolist()):
+            self.lookahead[v] = min(ms_to_samps(m), self.cap_lookahead)
+        self._dirty = True
+
+    def getLookAhead(self):
+        """H:2851-2853: sampsToMs divides two integers (H:949-952)."""
+        return (self.lookahead.astype(np.int64) // int(maxiSettings.sampleRate)) * 1000.0
+
+    def _set_window(self, ms, voices=None):
+        idx, ms = self._select(ms, voices)
+        for v, m in zip(idx.tolist(), ms.tolist()):
+            s = ms_to_samps(m)
+            if s <= self.cap_rms:         # maxiRMS::setWindowSize H:2590-2596: a request above the ring is ignored ...
+                self.window[v] = s
+            self._zero_running[v] = True  # ... but the running sum is zeroed either way (the ring is not)
+        self._dirty = True
+
+    def setRMSWindowSize(self, winSize, voices=None):
+        """H:2859-2861: min(winSize, 500) ms."""
+        self._set_window(np.minimum(np.asarray(winSize, np.float64), 500.0), voices)
+
+    def setInputAnalyser(self, mode, voices=None):
+        idx, m = self._select(mode, voices, np.int64)
+        self.analyser[idx] = np.where(m == self.PEAK, self.PEAK, self.RMS)
+        self._dirty = True
+
+
+class maxiDynamicsBank(_Bank, _DynControl):
+    """V x maxiDynamics (H:2625-2897).  `play(sig, control, thresholdHigh, ratioHigh, kneeHigh, thresholdLow, ratioLow,
+    kneeLow)` -> [N, V]; each parameter is a scalar, [V] or [N, V].  The setters take scalars or [V] arrays (the four
+    attack / release times are one value per bank: the envelopes share one shape).  State, all device buffers that can
+    be read and uploaded between blocks: rms_ring [cap_rms][V], la_ring [cap_lookahead][V], rms_pos / la_pos [V],
+    running [V], env_high / env_low = (dstate [5][V], istate [7][V]) as maxiEnvGenBank keeps them, overflow [V]."""
+
+    def __init__(self, voices, cap_rms=None, cap_lookahead=None, stream=None):
+        _Bank.__init__(self, voices, stream)
+        self._init_control(self.V, cap_rms, cap_lookahead)
+        self.rms_ring = DeviceBuffer((self.cap_rms, self.V))
+        self.la_ring = DeviceBuffer((self.cap_lookahead, self.V))
+        self.rms_pos = DeviceBuffer(self.V, np.int32)
+        self.la_pos = DeviceBuffer(self.V, np.int32)
+        self.running = DeviceBuffer(self.V)
+        self.overflow = DeviceBuffer(self.V, np.uint32)
+        d = np.zeros((5, self.V))
+        d[2:5] = 1.0
+        i = np.zeros((7, self.V), np.int64)
+        i[4:7] = 1
+        self.env_high = (DeviceBuffer.from_numpy(d), DeviceBuffer.from_numpy(i))
+        self.env_low = (DeviceBuffer.from_numpy(d), DeviceBuffer.from_numpy(i))
+        self.level_db = None
+
+    def _upload_control(self):
+        if self._zero_running.any():  # setWindowSize zeroes runningRMS of the voices it was called on
+            r = self.running.numpy()
+            r[self._zero_running] = 0.0
+            self.running.upload(r)
+            self._zero_running[:] = False
+        if self._dirty:
+            self._dwin, self._dla = DeviceBuffer.from_numpy(self.window), DeviceBuffer.from_numpy(self.lookahead)
+            self._dan = DeviceBuffer.from_numpy(self.analyser)
+            self._dsh, self._dsl = DeviceBuffer.from_numpy(self.stages_high), DeviceBuffer.from_numpy(self.stages_low)
+            self._dirty = False
+
+    def play(self, sig, control, thresholdHigh, ratioHigh, kneeHigh, thresholdLow, ratioLow, kneeLow, out=None,
+             want_level=False):
+        N = sig.shape[0]
+        _fx_dev(sig, np.float64, "sig", (N * self.V,))
+        if control is None:
+            control = sig
+        else:
+            _fx_dev(control, np.float64, "control", (N * self.V,))
+        pars, ps = [], 0
+        for name, x in zip(DYN_PS, (thresholdHigh, ratioHigh, kneeHigh, thresholdLow, ratioLow, kneeLow)):
+            b, per = _fx_param(x, self.V, N, np.float64, name)
+            pars.append(b)
+            ps |= per * DYN_PS[name]
+        self._upload_control()
+        out = self._out(N, out)
+        self.level_db = DeviceBuffer((N, self.V), zero=False) if want_level else None
+        check(lib().mxg_dynamics_render(self.V, N, _ptr(sig), _ptr(control), *[_ptr(b) for b in pars], ps,
+                                        self._dwin.ptr, self._dla.ptr, self._dan.ptr, self._dsh.ptr, self._dsl.ptr,
+                                        self.stages_high.shape[0], self.rms_ring.ptr, self.cap_rms, self.la_ring.ptr,
+                                        self.cap_lookahead, self.rms_pos.ptr, self.la_pos.ptr, self.running.ptr,
+                                        self.env_high[0].ptr, self.env_high[1].ptr, self.env_low[0].ptr,
+                                        self.env_low[1].ptr, self.overflow.ptr, _ptr(out), _ptr(self.level_db), self.stream),
+              "mxg_dynamics_render")
+        self._keep = (pars, sig, control)
+        return out
+
+    def compress(self, sig, threshold, ratio, knee, **kw):                    # H:2771-2773
+        return self.play(sig, None, threshold, ratio, knee, 0, 0, 0, **kw)
+
+    def sidechainCompress(self, sig, control, threshold, ratio, knee, **kw):  # H:2783-2785
+        return self.play(sig, control, threshold, ratio, knee, 0, 0, 0, **kw)
+
+    def compandAbove(self, sig, control, threshold, ratio, knee, **kw):       # H:2795-2797
+        return self.play(sig, control, threshold, ratio, knee, 0, 0, 0, **kw)
+
+    def compandBelow(self, sig, control, threshold, ratio, knee, **kw):       # H:2807-2809
+        return self.play(sig, control, 0, 0, 0, threshold, ratio, knee, **kw)
+
+
+class maxiRMSBank(_Bank):
+    """V x maxiRMS (H:2579-2616).  `cap` is the ring's size in samples (the reference's setup(maxLength, ...) in ms:
+    ms_to_samps).  State: ring [cap][V], pos [V], running [V], overflow [V]."""
+
+    def __init__(self, voices, cap, stream=None):
+        super().__init__(voices, stream)
+        self.cap = int(cap)
+        self.ring = DeviceBuffer((self.cap, self.V))
+        self.pos = DeviceBuffer(self.V, np.int32)
+        self.running = DeviceBuffer(self.V)
+        self.overflow = DeviceBuffer(self.V, np.uint32)
+        self.window = np.zeros(self.V, np.uint32)
+        self._dwin = None
+
+    def setup(self, maxLength, windowSize):
+        """H:2584-2587: a new zeroed ring of msToSamps(maxLength) slots, then setWindowSize."""
+        self.cap = ms_to_samps(maxLength)
+        self.ring = DeviceBuffer((self.cap, self.V))
+        self.pos = DeviceBuffer(self.V, np.int32)
+        self.setWindowSize(windowSize)
+
+    def setWindowSize(self, newWindowSize, voices=None):
+        """H:2590-2596; scalar or one value per voice of `voices` (None = all)."""
+        idx = np.arange(self.V)[slice(None) if voices is None else voices].reshape(-1)
+        ms = np.broadcast_to(np.asarray(newWindowSize, np.float64), idx.shape)
+        r = self.running.numpy()
+        for v, m in zip(idx.tolist(), ms.tolist()):
+            s = ms_to_samps(m)
+            if s <= self.cap:
+                self.window[v] = s
+            r[v] = 0.0
+        self.running.upload(r)
+        self._dwin = None
+
+    def play(self, x, out=None):
+        N = x.shape[0]
+        _fx_dev(x, np.float64, "input", (N * self.V,))
+        if self._dwin is None:
+            self._dwin = DeviceBuffer.from_numpy(self.window)
+        out = self._out(N, out)
+        check(lib().mxg_rms_render(self.V, N, _ptr(x), self._dwin.ptr, self.ring.ptr, self.cap, self.pos.ptr,
+                                   self.running.ptr, self.overflow.ptr, _ptr(out), self.stream), "mxg_rms_render")
+        return out
+
+
 SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAtSpeed": 4,
                 "playOnceAtSpeed": 5, "playUntilAtSpeed": 6, "play4": 7, "playAtSpeedBetweenPoints": 8,
                 # trigger-driven (mxg_sample_render_trig)
