@@ -325,7 +325,9 @@ __device__ __forceinline__ void osc_pipe_finish(const OscPipe<K> &p, double (&r)
 }
 
 // K samples at once where the waveform has the staged form (all LDS reads of the chunk in flight), tick by tick elsewhere
-template <int WF, int K>
+// FL: the table layout the caller's load_tab staged (bit 0, tab_copy: K1's sinebuf stages no copy and passes 0).  The staged form's phase
+// wrap is the three-instruction one whatever FL says: x - 0.0 is x, so its bits are the plain statement's (wrap_at_511).
+template <int WF, int K, int FL = kTickLean>
 __device__ __forceinline__ void osc_tick_chunk(double &phase, double &hold, const OscPre &q, const double *s_sine,
                                                const double *s_trans, double (&r)[K]) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -333,14 +335,14 @@ __device__ __forceinline__ void osc_tick_chunk(double &phase, double &hold, cons
         OscPipe<K> p;
         osc_pipe_phase<WF, K>(phase, q, p);
         __builtin_amdgcn_sched_barrier(0);
-        osc_pipe_fetch<WF, K>(p, WF == MXG_OSC_SINEBUF ? s_sine : s_trans);
+        osc_pipe_fetch<WF, K, FL>(p, WF == MXG_OSC_SINEBUF ? s_sine : s_trans);
         __builtin_amdgcn_sched_barrier(0);
         osc_pipe_finish<WF, K>(p, r, hold);
         return;
     }
 #endif
 #pragma unroll
-    for (int i = 0; i < K; i++) r[i] = osc_tick<WF, false, kTickLean>(phase, hold, q, s_sine, s_trans);
+    for (int i = 0; i < K; i++) r[i] = osc_tick<WF, false, FL>(phase, hold, q, s_sine, s_trans);
 }
 
 // The recurrence of one sample WITHOUT its output: exactly the phase operations of osc_tick, in its order.  For the

@@ -135,21 +135,25 @@ struct Pace {
 //   [5] / [6] the best period's phase and the period   [8] the clock at the end of the last phase
 // -- and ONE kernel that holds both loops.  Phases of 32 launches: free-running (clocks and caches settle), free-running (measured:
 // the device clock from the end of the previous phase's last launch to the end of its own -- the wall time, gaps included), then the
-// periods 31/32, 29/32, 27/32 of the starting one, DESCENDING towards the knee (measured at 0.83-0.9 of it), for as long as each phase
-// is shorter than the one before: below the knee a phase is 10-30 % longer, and the descent stops there.  The best period wins if it
-// beats the free-running phase by 2 %.  Where the free-running stream is the best (most boxes) the trial costs two phases a few
-// per cent slower than it: 0.1 % of a 2000-launch run.  After 16 384 launches it is repeated; a run shorter than 96 launches never
+// periods 31/32, 29/32, 27/32 of the starting one, DESCENDING towards the knee (measured at 0.83-0.9 of it), ALL THREE: below the knee
+// a phase is 10-30 % longer and simply loses.  (Until K1 rendered its chunks ahead the descent stopped at the first phase that was not
+// shorter than the one before it.  A phase is a wall time, with whatever gaps the host leaves in a stream's first launches: 3 runs
+// of 30 then stopped at 62 ticks, the slowest candidate, and ran at 45-46 us per block instead of 41: profiles/k1_render_ahead.md.)
+// The best period wins if it beats the free-running phase by 2 %.  Where the free-running stream is the best the trial costs three
+// phases a few per cent slower than it: 0.2 % of a 2000-launch run.  After 16 384 launches it is repeated; a run shorter than 96 launches never
 // leaves the free-running kernel it always had.
 constexpr unsigned kTrialPhase = 32, kTrialCandidates = 3, kTrialAgain = 16384 + 5 * kTrialPhase;  // (< 2^16: the count shares its word)
 
 struct PaceTrial {
     unsigned t_begin, n, period, tag;  // period: this launch's (0 = free-running); tag: the block length's low 16 bits (wall times of
                                        // different block lengths do not compare: another length starts the trial again)
+    unsigned verdict;                  // the verdict this launch started under (0: the trial is still running)
     __device__ __forceinline__ static unsigned candidate(unsigned arg, unsigned i) { return arg * (31u - 2u * i) / 32u; }  // i = 0, 1, 2: descending
     __device__ __forceinline__ void start(const unsigned *T, unsigned arg, unsigned block_len) {
         t_begin = Pace::now();
         n = 0;
         period = 0;
+        verdict = 0;
         tag = block_len & 0xffffu;
         if (T) {
             unsigned d = __hip_atomic_load(T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -159,6 +163,7 @@ struct PaceTrial {
                 n = 0;
                 d = 0;
             }
+            verdict = d;
             if (d) {
                 period = d >= 2 ? (d < 2 * arg ? d : 2 * arg) : 0;
             } else {
@@ -170,6 +175,15 @@ struct PaceTrial {
     // the end of the launch, one lane per workgroup
     __device__ __forceinline__ void finish(unsigned *T, unsigned arg, unsigned wg, unsigned nwg) const {
         if (!T || (wg & 15u)) return;
+        // Under a verdict a launch only COUNTS itself (the count shares word [1] with the tag: one addition, and below kTrialAgain no
+        // carry): one atomic that nobody waits for, from one workgroup.  The tickets below are round trips to memory at the very end of
+        // the kernel, behind its own store stream, and the last reporter's chain of them IS the kernel's tail (0.6 us of 41.7 per launch,
+        // profiles/k1_render_ahead.md): only a launch that may have something to judge -- a phase of the trial, or the launch that starts
+        // it again -- takes them.
+        if (verdict && n + 1 < kTrialAgain) {
+            if (wg == 0) __hip_atomic_fetch_add(&T[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
         const unsigned nrep = (nwg + 15u) / 16u;
         unsigned long long *acc = reinterpret_cast<unsigned long long *>(T + 2);
         const unsigned long long all = atomicAdd(acc, 1ull) + 1ull;  // (relaxed, one line, no fence: see Pace::finish)
@@ -187,14 +201,12 @@ struct PaceTrial {
                     atomicExch(&T[6], 0u);
                 } else if (ph >= 2) {
                     unsigned best = atomicAdd(&T[5], 0u), best_p = atomicAdd(&T[6], 0u);
-                    bool done = ph + 1 == 2 + kTrialCandidates;
+                    const bool done = ph + 1 == 2 + kTrialCandidates;
                     if (wall < best) {
                         best = wall;
                         best_p = candidate(arg, ph - 2);
                         atomicExch(&T[5], best);
                         atomicExch(&T[6], best_p);
-                    } else {
-                        done = true;  // longer than the period before it: that was the knee
                     }
                     if (done) d = ((unsigned long long)best * 100 < (unsigned long long)atomicAdd(&T[4], 0u) * 98) ? best_p : 1u;
                 }

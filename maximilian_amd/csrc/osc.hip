@@ -71,6 +71,28 @@ __device__ __forceinline__ void load_tab(double *s_tab) {  // (the caller synchr
     }
 }
 
+// One chunk of K1's paced schedule (mxg_pace.h): eight samples RENDERED AHEAD of their slot and stored ON it.  The ticks run in front of
+// the wait -- all table reads of the chunk in flight at once (osc_tick_chunk), at one wavefront per SIMD -- so that they fill the time the
+// wavefront would sleep anyway, and behind the wait there is nothing but the eight stores, back to back.  (Tick, store, tick, store behind
+// the wait is 113 VALU instructions at ~4.4 clk and eight exposed LDS round trips: the stores dribbled out over the whole period, the last
+// one nearly a period late, and nothing was left to catch up with: profiles/k1_render_ahead.md.)  The empty asm statements pin the
+// values in front of the wait: nothing else uses them there, and the compiler otherwise sinks the interpolations behind the wait loop.
+// Only operations of different samples change places: the bits are osc_tick's.  o: the lane's out + n * P + v, advanced by eight rows.
+template <int WF, int FL, int ST>
+__device__ __forceinline__ void paced_chunk(Pace &pc, double &ph, double &hd, const OscPre &q, const double *s_tab, double *&o, size_t P) {
+    double r[8];
+    osc_tick_chunk<WF, 8, FL>(ph, hd, q, s_tab, s_tab, r);
+#pragma unroll
+    for (int u = 0; u < 8; u++) asm volatile("" : "+v"(r[u]));
+    pc.wait(true);
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+        store1<ST>(o, r[u]);
+        o += P;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // K1: one lane = VPL adjacent voices; the N-sample recurrence runs in registers.
 // ST: store flavour (mxg_common.h: 0 plain, 1 nt, 2 sc1).  PX (VPL = 1): two samples per lane pair leave as one 16-byte store per
 // lane (store_pair_rows) -- every SIMD keeps its own wavefront of voices, and the store stream is the 16-byte one that the
@@ -195,14 +217,7 @@ __global__ void osc_kernel(size_t V, size_t N, const double *__restrict__ freq,
                 if (pc.P) {  // the paced schedule (mxg_pace.h): eight samples per slot, as non-temporal 8-byte stores (what the paced
                              // stream wants: profiles/r06_pace.md; this kernel's own pair rows are the free-running form)
                     double *o8 = out + nA * P + v0;
-                    for (; n + 8 <= nB; n += 8) {
-                        pc.wait(true);
-#pragma unroll
-                        for (int u = 0; u < 8; u++) {
-                            store1<1>(o8, osc_tick<WF, kTrust, kFL>(ph[0], hd[0], q[0], s_tab, s_tab));
-                            o8 += P;
-                        }
-                    }
+                    for (; n + 8 <= nB; n += 8) paced_chunk<WF, kFL, 1>(pc, ph[0], hd[0], q[0], s_tab, o8, P);
                     op += (n - nA) * P;
                 }
 #pragma unroll 2
@@ -228,14 +243,7 @@ __global__ void osc_kernel(size_t V, size_t N, const double *__restrict__ freq,
         }
         if constexpr (VPL == 1 && !FPS && !PX && !kLean) {
             if (pc.P) {  // the paced schedule, 8-byte store streams
-                for (; n + 8 <= nB; n += 8) {
-                    pc.wait(true);
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        store1<ST>(o, osc_tick<WF, kTrust, kFL>(ph[0], hd[0], q[0], s_tab, s_tab));
-                        o += P;
-                    }
-                }
+                for (; n + 8 <= nB; n += 8) paced_chunk<WF, kFL, ST>(pc, ph[0], hd[0], q[0], s_tab, o, P);
             }
         }
 #pragma unroll MXG_OSC_UNROLL
