@@ -1,0 +1,125 @@
+// include/maxiReverb.h -- drop-in maxiSatReverb, maxiFreeVerb and maxiFreeVerbStereo (the reference's src/libs/maxiReverb.h) over
+// mxg_reverb_render (K13): one bank-of-one launch per call, like maxiFlanger / maxiChorus in maximilian.h.
+//
+// Every call uploads its arguments (24 bytes), renders one voice and one sample on the library's stream and reads the one or two
+// output samples back.  A fresh object allocates, at its first call, only the ring slots the class ever touches (3 992 / 18 905 /
+// 12 587 doubles, at most 151 KB) rather than the reference's 23 MB of 44 100-slot rings.  The objects are value types: a copy
+// carries the rings, indices, low-pass states and (w, cut) device-to-device and continues from the same state.  After a device
+// failure every call returns silence; nothing throws.  What the reference computes is kept, quirks included (INTEGRATION.md
+// section 4): the stereo class's right channel is the allpass chain fed 0.0 on the left channel's rings, and its roomsize /
+// absorbtion change nothing.  maxiDattaroReverb is not provided.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "maximilian.h"
+
+namespace maxigpu {
+namespace ps {
+struct ReverbLine {
+    // one allocation: rings f64 [S] | lp f64 [8] | wc f64 [2] | args f64 [3] = in, roomsize, absorbtion | out f64 [2] | idx i32 [F]
+    int kind;
+    uint32_t S = 0, F = 0;
+    unsigned char *d = nullptr;
+    explicit ReverbLine(int k) : kind(k) {}
+    size_t bytes() const { return sizeof(double) * (S + 15) + sizeof(int32_t) * F; }
+    double *lp() const { return reinterpret_cast<double *>(d) + S; }
+    bool init() {
+        if (dead()) return false;
+        if (d) return true;
+        uint32_t nc = 0, na = 0;
+        if (!check(mxg_init(-1), "mxg_init") || !check(mxg_reverb_layout_host(kind, &nc, &na, &S, nullptr, nullptr), "mxg_reverb_layout_host"))
+            return false;
+        F = nc + na;
+        d = static_cast<unsigned char *>(mxg_malloc(bytes()));
+        if (!d) {
+            check(MXG_ERR_HIP, "mxg_malloc (reverb rings)");
+            return false;
+        }
+        const double wc[2] = {0.84, 0.2};  // a fresh maxiFreeVerb's comb weight and low-pass cutoff
+        return check(mxg_memset(d, 0, bytes(), nullptr), "mxg_memset") &&
+               check(mxg_memcpy_h2d(lp() + 8, wc, sizeof(wc), nullptr), "h2d reverb state") && check(mxg_sync(), "mxg_sync");
+    }
+    void release() {
+        if (d) mxg_free(d);
+        d = nullptr;
+    }
+    void copy_from(const ReverbLine &o) {
+        if (!o.d) {  // the source has not played yet: a fresh object again
+            release();
+            return;
+        }
+        if (!init()) return;
+        check(mxg_memcpy_d2d_async(d, o.d, bytes(), nullptr), "d2d reverb state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    // one sample; out[0], out[1] (the second only for the stereo kind)
+    void run(int mode, double x, double room, double absorb, double *out) {
+        out[0] = out[1] = 0.0;
+        if (!init()) return;
+        double *p = lp();
+        const double a[3] = {x, room, absorb};
+        if (!check(mxg_memcpy_h2d(p + 10, a, sizeof(a), nullptr), "h2d reverb arguments")) return;
+        const bool fv = kind == MXG_REVERB_FREEVERB;
+        if (!check(mxg_reverb_render(kind, mode, 1, 1, p + 10, p + 11, p + 12, 0, reinterpret_cast<double *>(d),
+                                     reinterpret_cast<int32_t *>(p + 15), fv ? p : nullptr, fv ? p + 8 : nullptr, p + 13, nullptr),
+                   "mxg_reverb_render"))
+            return;
+        double o[2] = {0.0, 0.0};
+        if (!check(mxg_memcpy_d2h(o, p + 13, sizeof(o), nullptr), "d2h reverb output")) return;
+        out[0] = o[0];
+        out[1] = kind == MXG_REVERB_FREEVERB_STEREO ? o[1] : 0.0;
+    }
+};
+}  // namespace ps
+}  // namespace maxigpu
+
+#define MAXIGPU_REVERB_VALUE_TYPE(Class, KIND)                       \
+    maxigpu::ps::ReverbLine line_{KIND};                             \
+    double stereooutput[2] = {0.0, 0.0};                             \
+                                                                     \
+public:                                                              \
+    Class() = default;                                               \
+    Class(const Class &o) { line_.copy_from(o.line_); }              \
+    Class &operator=(const Class &o) {                               \
+        if (this != &o) line_.copy_from(o.line_);                    \
+        return *this;                                                \
+    }                                                                \
+    ~Class() { line_.release(); }
+
+class maxiSatReverb {
+    MAXIGPU_REVERB_VALUE_TYPE(maxiSatReverb, MXG_REVERB_SAT)
+    double play(double input) {
+        line_.run(MXG_REVERB_PLAY, input, 0.0, 0.0, stereooutput);
+        return stereooutput[0];
+    }
+    double *playStereo(double input) {  // {b, -b}
+        line_.run(MXG_REVERB_PLAY, input, 0.0, 0.0, stereooutput);
+        stereooutput[1] = -stereooutput[0];
+        return stereooutput;
+    }
+};
+
+class maxiFreeVerb {
+    MAXIGPU_REVERB_VALUE_TYPE(maxiFreeVerb, MXG_REVERB_FREEVERB)
+    double play(double input) {  // the object's current comb weight and cutoff, 4 allpasses
+        line_.run(MXG_REVERB_PLAY, input, 0.0, 0.0, stereooutput);
+        return stereooutput[0];
+    }
+    double play(double input, double roomsize, double absorbtion) {  // sets both for good, 31 allpasses
+        line_.run(MXG_REVERB_PLAY_PARAMS, input, roomsize, absorbtion, stereooutput);
+        return stereooutput[0];
+    }
+};
+
+class maxiFreeVerbStereo {
+    MAXIGPU_REVERB_VALUE_TYPE(maxiFreeVerbStereo, MXG_REVERB_FREEVERB_STEREO)
+    double *playStereo(double input, double roomsize, double absorbtion) {  // (the reference reads neither parameter)
+        (void)roomsize;
+        (void)absorbtion;
+        line_.run(MXG_REVERB_PLAY, input, 0.0, 0.0, stereooutput);
+        return stereooutput;
+    }
+};
+
+#undef MAXIGPU_REVERB_VALUE_TYPE

@@ -466,6 +466,43 @@ int mxg_rms_render(size_t V, size_t N, const double *d_in, const uint32_t *d_win
  * setTime(0, ms) / setTime(2, ms).  Host arithmetic only: bit-exact. */
 int mxg_envgen_set_time_host(double *h_stages, size_t nstages, size_t index, double ms);
 
+/* ---- maxiSatReverb / maxiFreeVerb / maxiFreeVerbStereo (libs/maxiReverb.h, K13) ------------------------------------
+ * A bank of V reverbs.  Every delay length is a constant of the class (samples, independent of the sample rate):
+ *   MXG_REVERB_SAT              4 plain combs 778 901 1011 1123, 3 allpasses 125 42 12
+ *   MXG_REVERB_FREEVERB         8 low-pass combs 1557 1617 1491 1422 1277 1356 1188 1116, 31 allpasses 225 556 441 341 and
+ *                               13 * (j + 1) for j = 4 .. 30
+ *   MXG_REVERB_FREEVERB_STEREO  the same 8 combs, run plain, and the first 4 allpasses
+ * mxg_reverb_layout_host answers these per kind (any output may be NULL): the number of combs and allpasses, the doubles
+ * of ring state per voice (3 992 / 18 905 / 12 587) and, for filter f = 0 .. combs + allpasses - 1 (combs first), its
+ * length and its first slot inside the voice's ring area (lengths / offsets: room for MXG_REVERB_MAX_FILTERS).
+ * Carried state, caller-owned device memory, zero-initialised like the constructors: d_rings [V][ring_doubles]
+ * (VOICE-major; filter f of voice v at d_rings[v * ring_doubles + offsets[f]]), d_idx int32 [V][combs + allpasses] (the ring
+ * indices; one outside its ring restarts at slot 0), and for MXG_REVERB_FREEVERB d_lp [V][8] (the combs' low-pass states)
+ * and d_wc [V][2] = (w, cut), which a fresh object holds at (0.84, 0.2) -- not zero.  The other kinds take NULL there.
+ * d_in is [N][V]; d_out [N][V], for the stereo kind [2][N][V] (left, right).
+ * mode (MXG_REVERB_FREEVERB only, otherwise MXG_REVERB_PLAY): MXG_REVERB_PLAY = play(x): d_wc as it stands, 4 allpasses,
+ * the parameters are not read (NULL allowed).  MXG_REVERB_PLAY_PARAMS = play(x, roomsize, absorbtion): every sample first sets
+ * w = clamp01(roomsize * 0.10 + 0.84) and cut = clamp01(absorbtion) (a NaN stays a NaN), runs all 31 allpasses, and the last
+ * sample's (w, cut) stay in d_wc.  d_roomsize / d_absorbtion are [V], or [N][V] behind their MXG_REVERB_PS_* bit.
+ * What the reference computes is kept, quirks included: both filters run at 0.85 whatever gains the constructors store;
+ * the stereo class's right channel is the allpass chain fed 0.0 on the SAME four rings, a second step in the same sample,
+ * and its roomsize / absorbtion are read by nothing, so this entry point does not take them.
+ * Bit-exact (+ - * only, contraction off, subnormals kept): outputs and every piece of state. */
+#define MXG_REVERB_SAT 0
+#define MXG_REVERB_FREEVERB 1
+#define MXG_REVERB_FREEVERB_STEREO 2
+#define MXG_REVERB_PLAY 0
+#define MXG_REVERB_PLAY_PARAMS 1
+#define MXG_REVERB_PS_ROOMSIZE 1
+#define MXG_REVERB_PS_ABSORBTION 2
+#define MXG_REVERB_PS_ALL 3
+#define MXG_REVERB_MAX_FILTERS 39
+int mxg_reverb_layout_host(int kind, uint32_t *n_combs, uint32_t *n_allpasses, uint32_t *ring_doubles, uint32_t *lengths,
+                           uint32_t *offsets);
+int mxg_reverb_render(int kind, int mode, size_t V, size_t N, const double *d_in, const double *d_roomsize,
+                      const double *d_absorbtion, int ps_flags, double *d_rings, int32_t *d_idx, double *d_lp, double *d_wc,
+                      double *d_out, void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

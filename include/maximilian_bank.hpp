@@ -526,6 +526,85 @@ private:
     maxigpu::DeviceArray<double> fb_, depth_, coef_;
 };
 
+// ---- maxiSatReverb / maxiFreeVerb / maxiFreeVerbStereo banks (libs/maxiReverb.h, K13) --------------------------------------
+// Every delay length is a constant of the class; the state sizes come from mxg_reverb_layout_host.  Rings voice-major,
+// zeroed like the constructors.  Bit-exact, quirks of the reference included.
+class maxiReverbBankBase {
+public:
+    uint32_t combs() const { return nc_; }
+    uint32_t allpasses() const { return na_; }
+    uint32_t ringDoubles() const { return S_; }  // per voice
+    double *rings() { return rings_.get(); }     // device [V][ringDoubles()]
+    int32_t *indices() { return idx_.get(); }    // device [V][combs() + allpasses()]
+
+protected:
+    maxiReverbBankBase(int kind, size_t voices)
+        : kind_(kind), V(voices), nc_(layout(kind, 0)), na_(layout(kind, 1)), S_(layout(kind, 2)), rings_(voices * S_),
+          idx_(voices * (nc_ + na_)) {}
+    void render(int mode, size_t N, const double *d_in, const double *d_room, const double *d_absorb, double *d_lp, double *d_wc,
+                double *d_out, void *stream) {
+        maxigpu::check(mxg_reverb_render(kind_, mode, V, N, d_in, d_room, d_absorb, 0, rings_.get(), idx_.get(), d_lp, d_wc, d_out,
+                                         stream), "mxg_reverb_render");
+    }
+    int kind_;
+    size_t V;
+
+private:
+    static uint32_t layout(int kind, int which) {
+        uint32_t a[3] = {0, 0, 0};
+        maxigpu::check(mxg_reverb_layout_host(kind, &a[0], &a[1], &a[2], nullptr, nullptr), "mxg_reverb_layout_host");
+        return a[which];
+    }
+    uint32_t nc_, na_, S_;
+    maxigpu::DeviceArray<double> rings_;
+    maxigpu::DeviceArray<int32_t> idx_;
+};
+
+class maxiSatReverbBank : public maxiReverbBankBase {
+public:
+    explicit maxiSatReverbBank(size_t voices) : maxiReverbBankBase(MXG_REVERB_SAT, voices) {}
+    void play(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        render(MXG_REVERB_PLAY, N, d_in, nullptr, nullptr, nullptr, nullptr, d_out, stream);
+    }
+};
+
+class maxiFreeVerbBank : public maxiReverbBankBase {
+public:
+    explicit maxiFreeVerbBank(size_t voices)
+        : maxiReverbBankBase(MXG_REVERB_FREEVERB, voices), lp_(voices * 8), wc_(voices * 2), room_(voices), absorb_(voices) {
+        std::vector<double> wc(voices * 2);
+        for (size_t v = 0; v < voices; v++) {
+            wc[2 * v] = 0.84;  // a fresh object's comb weight and low-pass cutoff
+            wc[2 * v + 1] = 0.2;
+        }
+        wc_.upload(wc);
+    }
+    // play(x): the comb weight and cutoff as they stand, 4 allpasses
+    void play(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        render(MXG_REVERB_PLAY, N, d_in, nullptr, nullptr, lp_.get(), wc_.get(), d_out, stream);
+    }
+    // play(x, roomsize, absorbtion), one value per voice: sets both for good, 31 allpasses
+    void play(size_t N, const double *d_in, const std::vector<double> &roomsize, const std::vector<double> &absorbtion, double *d_out,
+              void *stream = nullptr) {
+        room_.upload(roomsize);
+        absorb_.upload(absorbtion);
+        render(MXG_REVERB_PLAY_PARAMS, N, d_in, room_.get(), absorb_.get(), lp_.get(), wc_.get(), d_out, stream);
+    }
+    double *weightAndCutoff() { return wc_.get(); }  // device [V][2]
+
+private:
+    maxigpu::DeviceArray<double> lp_, wc_, room_, absorb_;
+};
+
+class maxiFreeVerbStereoBank : public maxiReverbBankBase {
+public:
+    explicit maxiFreeVerbStereoBank(size_t voices) : maxiReverbBankBase(MXG_REVERB_FREEVERB_STEREO, voices) {}
+    // d_out [2][N][V]: left, right (the reference's roomsize / absorbtion change nothing and are not taken)
+    void playStereo(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        render(MXG_REVERB_PLAY, N, d_in, nullptr, nullptr, nullptr, nullptr, d_out, stream);
+    }
+};
+
 // ---- maxiDynamics (H:2625-2897) / maxiRMS (H:2579-2616) banks (K12): block-rate parameters per voice ------------------------
 // (per-sample parameters: call mxg_dynamics_render with ps_flags).  Rings slot-major, [capacity][V]; the defaults are the
 // reference's (500 ms and 1 s of samples at the sample rate in force at construction).  Times in ms as in the reference; the four

@@ -107,6 +107,9 @@ SIGNATURES = {
     "mxg_rms_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
     "mxg_envgen_set_time_host": (c_int, [c_void_p, c_size_t, c_size_t, c_double]),
+    "mxg_reverb_layout_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_reverb_render": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

@@ -802,6 +802,83 @@ class maxiChorusBank(_FxBank):
         return out
 
 
+REVERB_KINDS = {"sat": 0, "freeverb": 1, "freeverb_stereo": 2}  # MXG_REVERB_* (include/maxigpu.h)
+REVERB_PS = {"roomsize": 1, "absorbtion": 2}                    # MXG_REVERB_PS_*
+
+
+def reverb_layout(kind):
+    """(combs, allpasses, ring doubles per voice, lengths, offsets) of a reverb kind (mxg_reverb_layout_host)."""
+    nc, na, S = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    lens, offs = np.zeros(39, np.uint32), np.zeros(39, np.uint32)
+    check(lib().mxg_reverb_layout_host(int(kind), ctypes.addressof(nc), ctypes.addressof(na), ctypes.addressof(S),
+                                       lens.ctypes.data, offs.ctypes.data), "mxg_reverb_layout_host")
+    F = nc.value + na.value
+    return nc.value, na.value, S.value, lens[:F].astype(int).tolist(), offs[:F].astype(int).tolist()
+
+
+class _ReverbBank(_Bank):
+    """State of V reverbs (libs/maxiReverb.h): rings [V][ring doubles] (voice-major), idx int32 [V][filters]; the
+    constructors' zeros.  Ring state per voice: 3 992 / 18 905 / 12 587 doubles."""
+    KIND = 0
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        self.ncombs, self.nallpasses, self.ring_doubles, self.lengths, self.offsets = reverb_layout(self.KIND)
+        self.rings = DeviceBuffer((self.V, self.ring_doubles))
+        self.idx = DeviceBuffer((self.V, self.ncombs + self.nallpasses), np.int32)
+        self.lp = self.wc = None
+
+    def _render(self, mode, x, room, absorb, ps, channels, out):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        if out is None:
+            out = DeviceBuffer((N, self.V) if channels == 1 else (channels, N, self.V), np.float64, zero=False)
+        check(lib().mxg_reverb_render(self.KIND, mode, self.V, N, _ptr(x), _ptr(room), _ptr(absorb), ps, self.rings.ptr,
+                                      self.idx.ptr, _ptr(self.lp), _ptr(self.wc), _ptr(out), self.stream), "mxg_reverb_render")
+        self._keep = (room, absorb)
+        return out
+
+
+class maxiSatReverbBank(_ReverbBank):
+    """V x maxiSatReverb: 4 plain combs into 3 allpasses.  `play(x)` -> [N, V] (playStereo is (b, -b))."""
+    KIND = REVERB_KINDS["sat"]
+
+    def play(self, x, out=None):
+        return self._render(0, x, None, None, 0, 1, out)
+
+
+class maxiFreeVerbBank(_ReverbBank):
+    """V x maxiFreeVerb: 8 low-pass combs into 4 (`play(x)`) or 31 (`play(x, roomsize, absorbtion)`) allpasses, both on
+    the same rings.  The parameters are scalars, [V] or [N, V]; they set the comb weight and cutoff for good.  State
+    besides the rings: lp [V][8] (the combs' low-pass states), wc [V][2] = (w, cut), 0.84 and 0.2 in a fresh object."""
+    KIND = REVERB_KINDS["freeverb"]
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        self.lp = DeviceBuffer((self.V, 8))
+        self.wc = DeviceBuffer.from_numpy(np.tile(np.array([0.84, 0.2]), (self.V, 1)))
+
+    def play(self, x, roomsize=None, absorbtion=None, out=None):
+        if roomsize is None and absorbtion is None:
+            return self._render(0, x, None, None, 0, 1, out)
+        if roomsize is None or absorbtion is None:
+            raise TypeError("play(x, roomsize, absorbtion) takes both parameters")
+        N = x.shape[0]
+        r, pr = _fx_param(roomsize, self.V, N, np.float64, "roomsize")
+        a, pa = _fx_param(absorbtion, self.V, N, np.float64, "absorbtion")
+        return self._render(1, x, r, a, pr * REVERB_PS["roomsize"] | pa * REVERB_PS["absorbtion"], 1, out)
+
+
+class maxiFreeVerbStereoBank(_ReverbBank):
+    """V x maxiFreeVerbStereo.  `playStereo(x)` -> [2, N, V]: left = 8 plain combs into 4 allpasses, right = the same four
+    allpass rings stepped a second time with 0.0 (what the reference computes; its roomsize / absorbtion are read by nothing
+    and are accepted here only to be ignored)."""
+    KIND = REVERB_KINDS["freeverb_stereo"]
+
+    def playStereo(self, x, roomsize=None, absorbtion=None, out=None):
+        return self._render(0, x, None, None, 0, 2, out)
+
+
 DYN_PS = {"thresholdHigh": 1, "ratioHigh": 2, "kneeHigh": 4, "thresholdLow": 8, "ratioLow": 16, "kneeLow": 32}  # MXG_DYN_PS_*
 
 
