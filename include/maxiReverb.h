@@ -1,5 +1,6 @@
-// include/maxiReverb.h -- drop-in maxiSatReverb, maxiFreeVerb and maxiFreeVerbStereo (the reference's src/libs/maxiReverb.h) over
-// mxg_reverb_render (K13): one bank-of-one launch per call, like maxiFlanger / maxiChorus in maximilian.h.
+// include/maxiReverb.h -- drop-in maxiSatReverb, maxiFreeVerb, maxiFreeVerbStereo and maxiDattaroReverb (the reference's
+// src/libs/maxiReverb.h) over mxg_reverb_render (K13) and mxg_dattaro_render (K14): one bank-of-one launch per call, like
+// maxiFlanger / maxiChorus in maximilian.h.
 //
 // Every call uploads its arguments (24 bytes), renders one voice and one sample on the library's stream and reads the one or two
 // output samples back.  A fresh object allocates, at its first call, only the ring slots the class ever touches (3 992 / 18 905 /
@@ -7,7 +8,12 @@
 // carries the rings, indices, low-pass states and (w, cut) device-to-device and continues from the same state.  After a device
 // failure every call returns silence; nothing throws.  What the reference computes is kept, quirks included (INTEGRATION.md
 // section 4): the stereo class's right channel is the allpass chain fed 0.0 on the left channel's rings, and its roomsize /
-// absorbtion change nothing.  maxiDattaroReverb is not provided.
+// absorbtion change nothing.
+// maxiDattaroReverb fixes its ten delay lengths from maxiSettings::sampleRate in its constructor, in the reference's float
+// arithmetic; a later change of the sample rate does nothing to an existing object, and a copy keeps its source's lengths.  Its
+// rings (32 312 doubles at 44 100 Hz) are allocated at the first call.  The reference's 3 100-slot pre-delay ring is not carried:
+// its output is used by nothing and no call can observe it.  A sample rate the kernel does not accept (outside 3 345 ..
+// 295 129 Hz) prints one line and plays silence.  The helper class maxiReverbFilters is not provided.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -71,6 +77,51 @@ struct ReverbLine {
         out[1] = kind == MXG_REVERB_FREEVERB_STEREO ? o[1] : 0.0;
     }
 };
+struct DattaroLine {
+    // one allocation: rings f64 [S] | state f64 [5] | in f64 [1] | out f64 [2] | idx i32 [10]
+    uint32_t rate;
+    uint32_t S = 0;
+    unsigned char *d = nullptr;
+    DattaroLine() : rate(maxiSettings::sampleRate > 0xffffffffu ? 0xffffffffu : static_cast<uint32_t>(maxiSettings::sampleRate)) {}
+    size_t bytes() const { return sizeof(double) * (S + 8) + sizeof(int32_t) * MXG_DATTARO_RINGS; }
+    double *state() const { return reinterpret_cast<double *>(d) + S; }
+    bool init() {
+        if (dead()) return false;
+        if (d) return true;
+        if (!check(mxg_init(-1), "mxg_init") ||
+            !check(mxg_dattaro_layout_host(rate, nullptr, nullptr, &S, nullptr, nullptr), "mxg_dattaro_layout_host"))
+            return false;
+        d = static_cast<unsigned char *>(mxg_malloc(bytes()));
+        if (!d) {
+            check(MXG_ERR_HIP, "mxg_malloc (maxiDattaroReverb rings)");
+            return false;
+        }
+        return check(mxg_memset(d, 0, bytes(), nullptr), "mxg_memset") && check(mxg_sync(), "mxg_sync");
+    }
+    void release() {
+        if (d) mxg_free(d);
+        d = nullptr;
+    }
+    void copy_from(const DattaroLine &o) {  // the lengths are the source's, whatever the sample rate is now
+        if (!o.d || rate != o.rate) release();
+        rate = o.rate;
+        if (!o.d || !init()) return;  // (a source that has not played yet: a fresh object again)
+        check(mxg_memcpy_d2d_async(d, o.d, bytes(), nullptr), "d2d maxiDattaroReverb state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    void run(double x, double *out) {
+        out[0] = out[1] = 0.0;
+        if (!init()) return;
+        double *p = state();
+        if (!check(mxg_memcpy_h2d(p + 5, &x, sizeof(x), nullptr), "h2d maxiDattaroReverb input")) return;
+        if (!check(mxg_dattaro_render(rate, 1, 1, p + 5, reinterpret_cast<double *>(d), reinterpret_cast<int32_t *>(p + 8), p, p + 6, nullptr),
+                   "mxg_dattaro_render"))
+            return;
+        double o[2] = {0.0, 0.0};
+        if (!check(mxg_memcpy_d2h(o, p + 6, sizeof(o), nullptr), "d2h maxiDattaroReverb output")) return;
+        out[0] = o[0];
+        out[1] = o[1];
+    }
+};
 }  // namespace ps
 }  // namespace maxigpu
 
@@ -123,3 +174,21 @@ class maxiFreeVerbStereo {
 };
 
 #undef MAXIGPU_REVERB_VALUE_TYPE
+
+class maxiDattaroReverb {
+    maxigpu::ps::DattaroLine line_;  // (captures maxiSettings::sampleRate)
+    double stereooutput[2] = {0.0, 0.0};
+
+public:
+    maxiDattaroReverb() = default;
+    maxiDattaroReverb(const maxiDattaroReverb &o) { line_.copy_from(o.line_); }
+    maxiDattaroReverb &operator=(const maxiDattaroReverb &o) {
+        if (this != &o) line_.copy_from(o.line_);
+        return *this;
+    }
+    ~maxiDattaroReverb() { line_.release(); }
+    double *playStereo(double input) {
+        line_.run(input, stereooutput);
+        return stereooutput;
+    }
+};

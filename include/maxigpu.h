@@ -503,6 +503,40 @@ int mxg_reverb_render(int kind, int mode, size_t V, size_t N, const double *d_in
                       const double *d_absorbtion, int ps_flags, double *d_rings, int32_t *d_idx, double *d_lp, double *d_wc,
                       double *d_out, void *stream);
 
+/* ---- maxiDattaroReverb (libs/maxiReverb.h, K14) ---------------------------------------------------------------------
+ * A bank of V plate reverbs after Dattorro, stereo out.  Unlike the three classes above, every delay length follows the
+ * sample rate in force when the object is constructed, in the reference's float arithmetic:
+ *   floor(((float)orig / 29.8f) * ((float)sample_rate / 1000.0f)).
+ * A voice owns ten rings, in this order inside its ring area (orig, the length at 29.8 kHz, in brackets):
+ *   0 AP0 [142]   1 AP1 [107]      the input allpasses (fbap[0], fbap[1]), each stepped TWICE a sample
+ *   2 AP4 [908]   3 AP5 [2656]   4 AP6 [672]   5 AP7 [1800]     the tank allpasses (fbap[4 .. 7])
+ *   6 D0  [4217]  7 D1  [3163]   8 D2  [4453]  9 D3  [3720]     the tank delays
+ * and reads fourteen taps (orig 266 2974 1913 1996 1990 187 1066 353 3627 1228 2673 2111 335 121) from rings
+ * 6 6 3 7 8 5 9 8 8 5 9 6 3 7.  At 44 100 Hz: lengths 210 158 1343 3930 994 2663 6240 4680 6589 5505.
+ * mxg_dattaro_layout_host needs no device and answers, for a sample rate (any output may be NULL): lengths [10],
+ * offsets [10] (the ring's first slot inside the voice's ring area), the ring doubles per voice, tap_positions [14] and
+ * tap_rings [14].  A rate is accepted exactly when every length lies in [2, 44100] (the reference's ring size) and a
+ * tile of 64 samples is legal on rings 2 .. 9 (64 <= length) and on every tap (length - 1 - position is 0 or >= 64).
+ * That holds from 3 345 to 295 129 Hz except for 3 349 .. 3 360 and 3 374 .. 3 377; any other rate fails with
+ * MXG_ERR_INVALID and a message that names the range.
+ * Carried state, caller-owned device memory, all zero for a fresh object: d_rings [V][ring_doubles] (VOICE-major; ring r
+ * of voice v at d_rings[v * ring_doubles + offsets[r]]), d_idx int32 [V][10] (the ring indices; one outside its ring
+ * restarts at slot 0), d_state [V][5] = the three one-pole low-pass states lp0 lp1 lp2, then sigl, sigr (the tank's
+ * cross feedback).  d_in is [N][V]; d_out [2][N][V] (left, right).  The same sample_rate must accompany a bank for its
+ * whole life: the layout is a function of it.
+ * What the reference computes is kept, quirks included: the second input allpass pair runs on rings AP0 and AP1 again
+ * (fbap[2], fbap[3] are never touched), and gettap uses the index after the step.  The 3 100-slot pre-delay ring is
+ * written and read by every call, but its output is used by nothing and the ring is private: it cannot be observed, and
+ * the bank does not carry it.
+ * Bit-exact (+ - * only, contraction off, subnormals kept): outputs and every piece of state.  No CPU fallback. */
+#define MXG_DATTARO_RINGS 10
+#define MXG_DATTARO_TAPS 14
+#define MXG_DATTARO_STATE 5
+int mxg_dattaro_layout_host(uint32_t sample_rate, uint32_t *lengths, uint32_t *offsets, uint32_t *ring_doubles,
+                            uint32_t *tap_positions, uint32_t *tap_rings);
+int mxg_dattaro_render(uint32_t sample_rate, size_t V, size_t N, const double *d_in, double *d_rings, int32_t *d_idx,
+                       double *d_state, double *d_out, void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

@@ -605,6 +605,42 @@ public:
     }
 };
 
+// ---- maxiDattaroReverb bank (libs/maxiReverb.h, K14) -------------------------------------------------------------------------
+// Every delay length is fixed from `sampleRate` at construction, in the reference's float arithmetic (mxg_dattaro_layout_host;
+// a rate it does not accept throws).  Rings voice-major, everything zeroed like the constructor.  The reference's unobservable
+// pre-delay ring is not carried.  Bit-exact, quirks of the reference included.
+class maxiDattaroReverbBank {
+public:
+    explicit maxiDattaroReverbBank(size_t voices, uint32_t sampleRate = 44100)
+        : V(voices), rate_(sampleRate), lay_(sampleRate), rings_(voices * lay_.S), idx_(voices * MXG_DATTARO_RINGS),
+          state_(voices * MXG_DATTARO_STATE) {}
+    // d_in [N][V]; d_out [2][N][V]: left, right
+    void playStereo(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_dattaro_render(rate_, V, N, d_in, rings_.get(), idx_.get(), state_.get(), d_out, stream), "mxg_dattaro_render");
+    }
+    uint32_t sampleRate() const { return rate_; }
+    uint32_t ringDoubles() const { return lay_.S; }                    // per voice
+    const uint32_t *lengths() const { return lay_.len; }               // [10]: AP0 AP1 AP4 AP5 AP6 AP7 D0 D1 D2 D3
+    const uint32_t *offsets() const { return lay_.off; }               // [10]
+    const uint32_t *tapPositions() const { return lay_.tap; }          // [14]
+    const uint32_t *tapRings() const { return lay_.tapRing; }          // [14]
+    double *rings() { return rings_.get(); }                           // device [V][ringDoubles()]
+    int32_t *indices() { return idx_.get(); }                          // device [V][10]
+    double *state() { return state_.get(); }                           // device [V][5] = lp0 lp1 lp2 sigl sigr
+
+private:
+    struct Layout {
+        uint32_t len[MXG_DATTARO_RINGS], off[MXG_DATTARO_RINGS], tap[MXG_DATTARO_TAPS], tapRing[MXG_DATTARO_TAPS], S = 0;
+        explicit Layout(uint32_t rate) { maxigpu::check(mxg_dattaro_layout_host(rate, len, off, &S, tap, tapRing), "mxg_dattaro_layout_host"); }
+    };
+    size_t V;
+    uint32_t rate_;
+    Layout lay_;
+    maxigpu::DeviceArray<double> rings_;
+    maxigpu::DeviceArray<int32_t> idx_;
+    maxigpu::DeviceArray<double> state_;
+};
+
 // ---- maxiDynamics (H:2625-2897) / maxiRMS (H:2579-2616) banks (K12): block-rate parameters per voice ------------------------
 // (per-sample parameters: call mxg_dynamics_render with ps_flags).  Rings slot-major, [capacity][V]; the defaults are the
 // reference's (500 ms and 1 s of samples at the sample rate in force at construction).  Times in ms as in the reference; the four

@@ -9,7 +9,8 @@ from ._lib import LIB_PATH, MaxiGpuError, calib, lib  # noqa: F401
 from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, maxiEnvBank,  # noqa: F401
                     maxiVoiceBank, maxiMixBank, maxiDelaylineBank, maxiSampleBank, maxiDCBlockerBank,
                     maxiSVFBank, maxiBiquadBank, maxiEnvGenBank, maxiSamplerBank, maxiFlangerBank, maxiChorusBank, maxiDynamicsBank,
-                    maxiRMSBank, maxiSatReverbBank, maxiFreeVerbBank, maxiFreeVerbStereoBank, reverb_layout, OSC_WAVEFORMS,
+                    maxiRMSBank, maxiSatReverbBank, maxiFreeVerbBank, maxiFreeVerbStereoBank, reverb_layout, maxiDattaroReverbBank,
+                    dattaro_layout, OSC_WAVEFORMS,
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, frames_in_stream, padded_stream  # noqa: F401
 from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, WINDOWS  # noqa: F401

@@ -6,7 +6,7 @@ package imports or calls the CPU oracle under oracle/.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MXG_LIB") or os.path.join(_HERE, "libmaxigpu.so")  # (MXG_LIB: an A/B build of the same ABI, tools only)
@@ -110,6 +110,8 @@ SIGNATURES = {
     "mxg_reverb_layout_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_reverb_render": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_dattaro_layout_host": (c_int, [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_dattaro_render": (c_int, [c_uint32, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

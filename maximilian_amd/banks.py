@@ -879,6 +879,42 @@ class maxiFreeVerbStereoBank(_ReverbBank):
         return self._render(0, x, None, None, 0, 2, out)
 
 
+def dattaro_layout(sample_rate=44100):
+    """(lengths [10], offsets [10], ring doubles per voice, tap positions [14], tap rings [14]) of a maxiDattaroReverb
+    constructed at `sample_rate` (mxg_dattaro_layout_host; needs no device).  Raises for a rate outside the accepted range."""
+    S = ctypes.c_uint32()
+    lens, offs = np.zeros(10, np.uint32), np.zeros(10, np.uint32)
+    taps, rings = np.zeros(14, np.uint32), np.zeros(14, np.uint32)
+    check(lib().mxg_dattaro_layout_host(int(sample_rate), lens.ctypes.data, offs.ctypes.data, ctypes.addressof(S),
+                                        taps.ctypes.data, rings.ctypes.data), "mxg_dattaro_layout_host")
+    return (lens.astype(int).tolist(), offs.astype(int).tolist(), S.value, taps.astype(int).tolist(),
+            rings.astype(int).tolist())
+
+
+class maxiDattaroReverbBank(_Bank):
+    """V x maxiDattaroReverb (libs/maxiReverb.h, K14), every delay length fixed from `sample_rate` at construction as the
+    reference's constructor does.  `playStereo(x)` -> [2, N, V] (left, right).  State: rings [V][ring_doubles]
+    (voice-major, ring r at offsets[r]), idx int32 [V][10], state [V][5] = lp0 lp1 lp2 sigl sigr; all zero when fresh.
+    The reference's unobservable pre-delay ring is not carried."""
+
+    def __init__(self, voices, sample_rate=44100, stream=None):
+        super().__init__(voices, stream)
+        self.sample_rate = int(sample_rate)
+        self.lengths, self.offsets, self.ring_doubles, self.tap_positions, self.tap_rings = dattaro_layout(self.sample_rate)
+        self.rings = DeviceBuffer((self.V, self.ring_doubles))
+        self.idx = DeviceBuffer((self.V, 10), np.int32)
+        self.state = DeviceBuffer((self.V, 5))
+
+    def playStereo(self, x, out=None):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        if out is None:
+            out = DeviceBuffer((2, N, self.V), np.float64, zero=False)
+        check(lib().mxg_dattaro_render(self.sample_rate, self.V, N, _ptr(x), self.rings.ptr, self.idx.ptr, self.state.ptr,
+                                       _ptr(out), self.stream), "mxg_dattaro_render")
+        return out
+
+
 DYN_PS = {"thresholdHigh": 1, "ratioHigh": 2, "kneeHigh": 4, "thresholdLow": 8, "ratioLow": 16, "kneeLow": 32}  # MXG_DYN_PS_*
 
 
