@@ -137,8 +137,15 @@ int mxg_prof_overhead_ms(void *stream, int pairs, double *h_ms);
  * mfcc within 5e-4 of the reference's; bit-exactness is given up, accuracy is gained),
  * "time_parallel" (the other exception to "identical results": 1 lets banks of at most 4096 linear filters with block-constant
  * coefficients -- maxiBiquad, maxiSVF, maxiDCBlocker through mxg_filter2_render, lores / hires through mxg_filter_render -- and blocks
- * of 64 * {1..32} samples be cut along time and joined by a wavefront scan: a 6-voice x 512-sample block in a few microseconds
- * instead of 23-28, with reordered arithmetic: |error| <= 1e-10 x the block's peak (measured <= 5e-12); default 0 = the bit-exact kernels),
+ * of 64, 128, 256, 512, 1024 or 2048 samples (64 x a power of two up to 32; every other block length keeps the bit-exact kernels) be
+ * cut along time and joined by a wavefront scan: a 6-voice x 512-sample block in a few microseconds instead of 23-28, with reordered
+ * arithmetic: |error| <= 1e-10 x the voice's peak of the sequential output over the carried blocks, for stable settings and finite
+ * input, over the whole domain the classes accept (measured on the 64-lane host build of csrc/mxg_scan.h, whose bits the device
+ * must give: <= 6.3e-11 for maxiBiquad -- at 10 Hz, N = 2048, where the float64 sequential recurrence is itself 3.8e-11 from a
+ * long-double one; <= 1.4e-11 up to N = 512 -- and <= 8e-14 for the other kinds).  The biquad's scan is carried in (v2, v1, v1 - v2),
+ * which is what
+ * holds the bound at 10 ... 60 Hz.  A setting at which the reference itself diverges (lores at 10 kHz with resonance 1) is outside
+ * the bound; such a voice, like one fed a NaN or an infinity, changes no other voice's bits.  default 0 = the bit-exact kernels),
  * "osc_plan" (K1, banks beyond ~350 MB per block: rendered as passes of 98 304 voices + a remainder launch; 0 automatic, 1 never, 2 / 3 always),
  * "osc_passes" / "osc_mix_passes" (K1 / K1m: voice groups a wavefront renders one after the other, the grid covering 1 / passes of the bank: 0 automatic, 1..64),
  * "osc_split" (time parts per voice group in K1: 0 automatic, 1..8), "osc_mix_split" (the same for the fused render + mixdown K1m,

@@ -1,11 +1,11 @@
 """CPU (-m "not gpu"): the host builds of the device headers (mxg_env.h, mxg_envgen.h, mxg_osc.h, mxg_smp.h, mxg_sched.h /
-mxg_advance.h -- plain arithmetic shared with the kernels) once more under UndefinedBehaviorSanitizer."""
+mxg_advance.h, mxg_scan.h -- plain arithmetic shared with the kernels) once more under UndefinedBehaviorSanitizer."""
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SUITES = ["test_env_host.py", "test_envgen_host.py", "test_osc_host.py", "test_smp_host.py", "test_sched_host.py"]
+SUITES = ["test_env_host.py", "test_envgen_host.py", "test_osc_host.py", "test_smp_host.py", "test_sched_host.py", "test_scan_host.py"]
 
 
 def test_host_harnesses_are_ubsan_clean():
