@@ -544,6 +544,61 @@ int mxg_dattaro_layout_host(uint32_t sample_rate, uint32_t *lengths, uint32_t *o
 int mxg_dattaro_render(uint32_t sample_rate, size_t V, size_t N, const double *d_in, double *d_rings, int32_t *d_idx,
                        double *d_state, double *d_out, void *stream);
 
+/* ---- sequencers: maxiRatioSeq / maxiStep / maxiCounter / maxiIndex / maxiZXToPulse / maxiTrigger::onZX (K15) ---------
+ * (H:564-596, 1953-2013, 2093-2262.)  Compares, + - / floor and integer indexing only: every output and every state array is
+ * BIT-EXACT.  The one departure: a table read index is held inside its table where the reference would index out of bounds
+ * (maxiStep with step < -len, a NaN index, an uploaded state out of range).
+ *
+ * Tables are block-constant; a caller changes them between blocks.  A table is doubles [P][L] with int32 lengths [P] (row p
+ * counts its first len[p] entries; a length is held in [1, L] on the device).  A voice picks its row with an int32 [V]
+ * selector (NULL = row 0 for every voice; held in [0, P - 1]).  All tables of one call fit 48 KB.
+ *
+ * mxg_seq_ratio_host: maxiRatioSeq::playTrig's boundaries (H:2172-2186) for P patterns of at most L <= 64 ratios, on the host,
+ * the reference's operations in the reference's order: h_norm[p][i] = (times[0] + ... + times[i]) / sum, a boundary equal to 1.0
+ * becomes 0.0; entries past h_len[p] are NaN (never fire).  Refuses L > 64 and a length < 1 or > L.
+ *
+ * mxg_seq_render, the fused sequencer, per voice and sample:
+ *     phase = maxiOsc::phasor(d_freq[v])                    internal clock: d_freq [V], d_clk [V] = maxiOsc::phase, in/out --
+ *                                                           bit for bit mxg_osc_render(MXG_OSC_PHASOR); d_phase NULL
+ *           | d_phase[n][v] (phase_pv = 1) | d_phase[n] (phase_pv = 0)      external clock: d_freq and d_clk NULL
+ *     trig  = maxiRatioSeq::playTrig(phase, pattern d_pat[v] of d_norm / d_len [P][L])            -> d_trig [N][V]
+ *     val   = playValues(phase, pattern, values)                      val_mode MXG_SEQ_VAL_VALUES
+ *           | maxiStep::pull(trig, values, d_step[v])                 val_mode MXG_SEQ_VAL_STEP   -> d_val  [N][V]
+ *             with values = list d_vpat[v] of d_values / d_vlen [PV][LV]; d_step NULL = 1
+ *     gate  = maxiZXToPulse::play(trig, d_hold[v])  (samples; d_hold NULL = 0)                     -> d_gate [N][V]
+ * Each output is optional (at least one): a stage whose output is NULL does not run and its state is untouched; playTrig always
+ * runs.  d_trig / d_gate are what mxg_envgen_render reads with tpv = 1, d_val what mxg_osc_render reads with fps = 1.
+ * State, in/out: d_dst [5][V] doubles = maxiRatioSeq::prevPhase | maxiStep: trig.previousValue, index |
+ * maxiZXToPulse: trig.previousValue, holdCounter;  d_ist [6][V] int64 = maxiRatioSeq: first, counter, lengthOfValues |
+ * maxiStep: trig.firstTrigger, first | maxiZXToPulse: trig.firstTrigger.  Fresh objects: all zero except previousValue = 1.0
+ * (d_dst rows 1, 3) and the four first flags = 1 (d_ist rows 0, 3, 4, 5).  1 / sampleRate is read at the call (mxg_settings).
+ *
+ * mxg_seq_signal: one of the classes driven by the caller's signals, d_in / d_in2 / d_out [N][V] (d_out distinct from the inputs):
+ *     MXG_SEQ_ONZX       maxiTrigger::onZX(d_in)                       d_dst: previousValue                 d_ist: firstTrigger
+ *     MXG_SEQ_COUNTER    maxiCounter::count(d_in, d_in2)               value, inc.previousValue, rst.previousValue | inc.first, rst.first
+ *     MXG_SEQ_STEP       maxiStep::pull(d_in, values, d_par[v])        trig.previousValue, index            | trig.firstTrigger, first
+ *     MXG_SEQ_INDEX      maxiIndex::pull(d_in, d_in2, values)          trig.previousValue, value            | trig.firstTrigger
+ *     MXG_SEQ_ZXTOPULSE  maxiZXToPulse::play(d_in, d_par[v])           trig.previousValue, holdCounter      | trig.firstTrigger
+ * d_dst is [3][V] doubles and d_ist [2][V] int64 for every kind (rows a kind does not use are left alone); fresh objects:
+ * every previousValue 1.0, every first flag 1, the rest 0.  d_par NULL = step 1 / hold 0. */
+#define MXG_SEQ_MAX_RATIOS 64
+#define MXG_SEQ_VAL_VALUES 0
+#define MXG_SEQ_VAL_STEP 1
+#define MXG_SEQ_ONZX 0
+#define MXG_SEQ_COUNTER 1
+#define MXG_SEQ_STEP 2
+#define MXG_SEQ_INDEX 3
+#define MXG_SEQ_ZXTOPULSE 4
+int mxg_seq_ratio_host(size_t P, size_t L, const int32_t *h_len, const double *h_times, double *h_norm);
+int mxg_seq_render(size_t V, size_t N, const double *d_freq, double *d_clk, const double *d_phase, int phase_pv,
+                   const double *d_norm, const int32_t *d_len, size_t P, size_t L, const int32_t *d_pat, int val_mode,
+                   const double *d_values, const int32_t *d_vlen, size_t PV, size_t LV, const int32_t *d_vpat,
+                   const double *d_step, const double *d_hold, double *d_dst, int64_t *d_ist, double *d_trig, double *d_val,
+                   double *d_gate, void *stream);
+int mxg_seq_signal(int kind, size_t V, size_t N, const double *d_in, const double *d_in2, const double *d_values,
+                   const int32_t *d_vlen, size_t PV, size_t LV, const int32_t *d_vpat, const double *d_par, double *d_dst,
+                   int64_t *d_ist, double *d_out, void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

@@ -1393,6 +1393,139 @@ public:
     inline T value() const { return val; }
 };
 
+// ---- maxiCounter (H:1953-1977), maxiIndex (H:1982-2013), maxiStep (H:2093-2141), maxiRatioSeq (H:2146-2230), maxiZXToPulse
+// (H:2235-2262): the reference's control-rate sequencing helpers, host value types like maxiTrigger -- a patch calls them once
+// per sample between its unit generators, and their outputs feed those as plain arguments.  The same arithmetic as the banks'
+// (maximilian_amd/csrc/mxg_seq.h, kernel K15): compares, + - / floor and indexing, the reference's bits.  maxiSettings::sampleRate
+// is read at the call.  The one departure: a read index is held inside the list where the reference would index out of bounds
+// (maxiStep with step < -length, a NaN index); an empty list reads 0.
+namespace maxigpu {
+namespace ps {
+inline double seq_at(const std::vector<double> &values, double index) {
+    if (values.empty()) return 0.0;
+    if (!(index >= 1.0)) return values[0];
+    if (index >= (double)values.size()) return values.back();
+    return values[static_cast<size_t>(index)];
+}
+}  // namespace ps
+}  // namespace maxigpu
+
+class maxiCounter {
+public:
+    double count(double incTrigger, double resetTrigger) {  // H:1961-1972: increments before it resets
+        if (inctrig.onZX(incTrigger)) value++;
+        if (rstrig.onZX(resetTrigger)) value = 0;
+        return value;
+    }
+
+private:
+    double value = 0;
+    maxiTrigger inctrig, rstrig;
+};
+
+class maxiIndex {
+public:
+    double pull(const double trigSig, double indexSig, vector<double> &values) {  // H:1992-2008
+        if (trig.onZX(trigSig)) {
+            if (indexSig < 0) indexSig = 0;
+            if (indexSig > 1) indexSig = 1;
+            value = maxigpu::ps::seq_at(values, floor(indexSig * 0.99999999 * values.size()));
+        }
+        return value;
+    }
+
+private:
+    maxiTrigger trig;
+    double value = 0;
+};
+
+class maxiStep {
+public:
+    double pull(const double trigSig, vector<double> values, double step) {  // H:2103-2130
+        if (trig.onZX(trigSig)) {
+            if (first) {  // the first trigger reads the list's start without stepping
+                first = false;
+                index = 0;
+            } else {
+                const auto arrayLen = values.size();
+                if (step > arrayLen) step = arrayLen;
+                index = index + step;
+                if (index < 0) index = arrayLen + index;
+                else if (index >= arrayLen) index = index - arrayLen;
+            }
+        }
+        return maxigpu::ps::seq_at(values, index);  // on every sample, not only on triggers
+    }
+    double getIndex() { return index; }
+
+private:
+    maxiTrigger trig;
+    bool first = true;
+    double index = 0;
+};
+
+class maxiRatioSeq {
+public:
+    double playTrig(double phase, vector<double> times) { return trigger(phase, times); }  // H:2165-2195
+    double playValues(double phase, vector<double> &times, vector<double> &values) {    // H:2204-2223
+        const size_t vallen = values.size();
+        if (lengthOfValues != vallen) {  // before the trigger is looked at
+            lengthOfValues = vallen;
+            counter = lengthOfValues - 1;
+        }
+        if (trigger(phase, times)) {
+            counter++;
+            if (counter == vallen) counter = 0;
+        }
+        return maxigpu::ps::seq_at(values, (double)counter);
+    }
+
+private:
+    double trigger(double phase, const vector<double> &times) {
+        const double tick = 1.0 / maxiSettings::sampleRate;
+        if (first) {
+            first = false;
+            prevPhase = phase - tick;
+        }
+        double sum = 0;
+        for (double t : times) sum += t;
+        if (prevPhase > phase) prevPhase = -tick;  // the clock wrapped
+        double trig = 0, accumulatedTime = 0;
+        for (double t : times) {
+            accumulatedTime += t;
+            double normalisedTime = accumulatedTime / sum;
+            if (normalisedTime == 1.0) normalisedTime = 0.0;
+            if (prevPhase <= normalisedTime && phase > normalisedTime) {
+                trig = 1;
+                break;
+            }
+        }
+        prevPhase = phase;
+        return trig;
+    }
+    double prevPhase = 0;
+    size_t counter = 0;
+    size_t lengthOfValues = 0;
+    bool first = true;
+};
+
+class maxiZXToPulse {
+public:
+    double play(double input, double holdTimeInSamples) {  // H:2245-2258
+        double output = 0;
+        if (trig.onZX(input)) holdCounter = holdTimeInSamples;
+        if (holdCounter > 0) {
+            output = 1;
+            holdCounter--;
+        }
+        return output;
+    }
+
+private:
+    maxiTrigger trig;
+    double holdCounter = 0;
+};
+
 // ---- maxiSample (H:602-790; C:605-1075): the play family over a buffer uploaded once ---------------------------------
 // The buffer lives on the device.  The members that EDIT it (normalise, autoTrim, loopRecord) work on a host copy fetched on
 // first use and write back what they changed -- setup-time utilities of the reference, not the per-sample path -- with the

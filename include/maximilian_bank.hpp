@@ -760,6 +760,158 @@ private:
     maxigpu::DeviceArray<uint32_t> ovf_, win_;
 };
 
+// ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
+namespace maxigpu {
+// lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device
+class SeqTable {
+public:
+    void set(const std::vector<std::vector<double>> &rows, bool ratios) {
+        if (rows.empty()) throw std::runtime_error("SeqTable: no list");
+        P = rows.size();
+        L = 0;
+        for (const auto &r : rows) L = r.size() > L ? r.size() : L;
+        std::vector<double> tab(P * L, 0.0);
+        std::vector<int32_t> len(P);
+        for (size_t p = 0; p < P; p++) {
+            if (rows[p].empty()) throw std::runtime_error("SeqTable: an empty list");
+            len[p] = (int32_t)rows[p].size();
+            for (size_t i = 0; i < rows[p].size(); i++) tab[p * L + i] = rows[p][i];
+        }
+        if (ratios) {  // maxiRatioSeq::playTrig's boundaries, on the host
+            std::vector<double> norm(P * L);
+            check(mxg_seq_ratio_host(P, L, len.data(), tab.data(), norm.data()), "mxg_seq_ratio_host");
+            tab.swap(norm);
+        }
+        tab_.resize(tab.size(), false);
+        tab_.upload(tab);
+        len_.resize(len.size(), false);
+        len_.upload(len);
+    }
+    const double *tab() const { return tab_.get(); }
+    const int32_t *len() const { return len_.get(); }
+    size_t P = 0, L = 0;
+
+private:
+    DeviceArray<double> tab_;
+    DeviceArray<int32_t> len_;
+};
+}  // namespace maxigpu
+
+// V fused sequencers: clock -> maxiRatioSeq::playTrig -> playValues | maxiStep::pull -> maxiZXToPulse::play (mxg_seq_render).
+// Patterns and value lists are block-constant; per voice: setPattern / setValueList / setStep / setHold.  The output blocks are
+// what maxiEnvGenBank::play (per_voice) and mxg_osc_render (fps = 1) read.
+class maxiSeqBank {
+public:
+    enum ValueMode { VALUES = MXG_SEQ_VAL_VALUES, STEP = MXG_SEQ_VAL_STEP };
+    maxiSeqBank(size_t voices, const std::vector<std::vector<double>> &times, const std::vector<std::vector<double>> &values = {})
+        : V(voices), clk_(voices), dst_(5 * voices), ist_(6 * voices) {
+        std::vector<double> d(5 * V, 0.0);
+        std::vector<int64_t> i(6 * V, 0);
+        for (size_t v = 0; v < V; v++) { d[V + v] = d[3 * V + v] = 1.0; i[v] = i[3 * V + v] = i[4 * V + v] = i[5 * V + v] = 1; }
+        dst_.upload(d); ist_.upload(i);
+        setTimes(times);
+        if (!values.empty()) setValues(values);
+    }
+    void setTimes(const std::vector<std::vector<double>> &times) { pat_.set(times, true); }
+    void setValues(const std::vector<std::vector<double>> &values) { val_.set(values, false); }
+    void setPattern(const std::vector<int32_t> &sel) { sel_.upload(sel); has_sel_ = true; }
+    void setValueList(const std::vector<int32_t> &sel) { vsel_.upload(sel); has_vsel_ = true; }
+    void setStep(const std::vector<double> &step) { step_.upload(step); has_step_ = true; }
+    void setHold(const std::vector<double> &samples) { hold_.upload(samples); has_hold_ = true; }
+    // internal clock maxiOsc::phasor(d_freq[v]); any of d_trig / d_val / d_gate may be null (that stage does not run)
+    void render(size_t N, const double *d_freq, double *d_trig, double *d_val, double *d_gate, ValueMode mode = VALUES,
+                void *stream = nullptr) {
+        run(N, d_freq, clk_.get(), nullptr, 0, d_trig, d_val, d_gate, mode, stream);
+    }
+    // external clock: d_phase [N][V] (per_voice) or one shared [N]
+    void renderPhase(size_t N, const double *d_phase, bool per_voice, double *d_trig, double *d_val, double *d_gate,
+                     ValueMode mode = VALUES, void *stream = nullptr) {
+        run(N, nullptr, nullptr, d_phase, per_voice ? 1 : 0, d_trig, d_val, d_gate, mode, stream);
+    }
+    double *clockPhase() { return clk_.get(); }
+    double *stateDoubles() { return dst_.get(); }
+    int64_t *stateInts() { return ist_.get(); }
+
+private:
+    void run(size_t N, const double *f, double *clk, const double *ph, int pv, double *t, double *x, double *g, ValueMode mode, void *stream) {
+        maxigpu::check(mxg_seq_render(V, N, f, clk, ph, pv, pat_.tab(), pat_.len(), pat_.P, pat_.L, has_sel_ ? sel_.get() : nullptr, mode,
+                                      val_.tab(), val_.len(), val_.P, val_.L, has_vsel_ ? vsel_.get() : nullptr,
+                                      has_step_ ? step_.get() : nullptr, has_hold_ ? hold_.get() : nullptr, dst_.get(), ist_.get(), t, x, g,
+                                      stream), "mxg_seq_render");
+    }
+    size_t V;
+    maxigpu::SeqTable pat_, val_;
+    maxigpu::DeviceArray<double> clk_, dst_, step_, hold_;
+    maxigpu::DeviceArray<int64_t> ist_;
+    maxigpu::DeviceArray<int32_t> sel_, vsel_;
+    bool has_sel_ = false, has_vsel_ = false, has_step_ = false, has_hold_ = false;
+};
+
+namespace maxigpu {
+// one of the reference's sequencing classes driven by device signals [N][V] (mxg_seq_signal)
+class SeqSignalBank {
+public:
+    void setValues(const std::vector<std::vector<double>> &values) { val_.set(values, false); }
+    void setValueList(const std::vector<int32_t> &sel) { vsel_.upload(sel); has_vsel_ = true; }
+
+protected:
+    SeqSignalBank(int kind, size_t voices) : kind_(kind), V(voices), dst_(3 * voices), ist_(2 * voices) {
+        std::vector<double> d(3 * V, 0.0);
+        std::vector<int64_t> i(2 * V, 0);
+        for (size_t v = 0; v < V; v++) {  // every maxiTrigger: previousValue = 1, firstTrigger = 1; maxiStep::first = true
+            if (kind == MXG_SEQ_COUNTER) { d[V + v] = d[2 * V + v] = 1.0; i[v] = i[V + v] = 1; }
+            else { d[v] = 1.0; i[v] = 1; if (kind == MXG_SEQ_STEP) i[V + v] = 1; }
+        }
+        dst_.upload(d); ist_.upload(i);
+    }
+    void run(size_t N, const double *a, const double *b, const double *par, double *out, void *stream) {
+        check(mxg_seq_signal(kind_, V, N, a, b, val_.tab(), val_.len(), val_.P, val_.L, has_vsel_ ? vsel_.get() : nullptr, par, dst_.get(),
+                             ist_.get(), out, stream), "mxg_seq_signal");
+    }
+    int kind_;
+    size_t V;
+    SeqTable val_;
+    DeviceArray<double> dst_;
+    DeviceArray<int64_t> ist_;
+    DeviceArray<int32_t> vsel_;
+    bool has_vsel_ = false;
+};
+}  // namespace maxigpu
+
+class maxiTriggerBank : public maxigpu::SeqSignalBank {  // maxiTrigger::onZX
+public:
+    explicit maxiTriggerBank(size_t voices) : SeqSignalBank(MXG_SEQ_ONZX, voices) {}
+    void onZX(size_t N, const double *d_in, double *d_out, void *stream = nullptr) { run(N, d_in, nullptr, nullptr, d_out, stream); }
+};
+class maxiCounterBank : public maxigpu::SeqSignalBank {  // maxiCounter::count
+public:
+    explicit maxiCounterBank(size_t voices) : SeqSignalBank(MXG_SEQ_COUNTER, voices) {}
+    void count(size_t N, const double *d_inc, const double *d_reset, double *d_out, void *stream = nullptr) {
+        run(N, d_inc, d_reset, nullptr, d_out, stream);
+    }
+};
+class maxiStepBank : public maxigpu::SeqSignalBank {  // maxiStep::pull; d_step [V] (null = 1)
+public:
+    maxiStepBank(size_t voices, const std::vector<std::vector<double>> &values) : SeqSignalBank(MXG_SEQ_STEP, voices) { setValues(values); }
+    void pull(size_t N, const double *d_trig, const double *d_step, double *d_out, void *stream = nullptr) {
+        run(N, d_trig, nullptr, d_step, d_out, stream);
+    }
+};
+class maxiIndexBank : public maxigpu::SeqSignalBank {  // maxiIndex::pull
+public:
+    maxiIndexBank(size_t voices, const std::vector<std::vector<double>> &values) : SeqSignalBank(MXG_SEQ_INDEX, voices) { setValues(values); }
+    void pull(size_t N, const double *d_trig, const double *d_index, double *d_out, void *stream = nullptr) {
+        run(N, d_trig, d_index, nullptr, d_out, stream);
+    }
+};
+class maxiZXToPulseBank : public maxigpu::SeqSignalBank {  // maxiZXToPulse::play; d_hold [V] samples (null = 0)
+public:
+    explicit maxiZXToPulseBank(size_t voices) : SeqSignalBank(MXG_SEQ_ZXTOPULSE, voices) {}
+    void play(size_t N, const double *d_in, const double *d_hold, double *d_out, void *stream = nullptr) {
+        run(N, d_in, nullptr, d_hold, d_out, stream);
+    }
+};
+
 // ---- maxiSample play family (H:602-783): V play heads over one sample ---------------------------------------
 class maxiSampleBank {
 public:

@@ -112,6 +112,10 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_dattaro_layout_host": (c_int, [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_dattaro_render": (c_int, [c_uint32, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_seq_ratio_host": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mxg_seq_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                               c_int, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 9),
+    "mxg_seq_signal": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 6),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

@@ -1129,6 +1129,179 @@ SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAt
                 "playOnZXAtSpeedBetweenPoints": 12, "loopSetPosOnZX": 13, "playWithPhasor": 14}
 
 
+def seq_table(rows, width=None):
+    """Ragged lists -> (doubles [P][L], int32 lengths [P]): the table form of mxg_seq_render / mxg_seq_signal."""
+    rows = [list(np.atleast_1d(np.asarray(r, np.float64))) for r in rows]
+    if not rows or min(len(r) for r in rows) < 1:
+        raise ValueError("a table needs at least one list and every list at least one entry")
+    width = max(len(r) for r in rows) if width is None else int(width)
+    tab = np.zeros((len(rows), width))
+    for i, r in enumerate(rows):
+        tab[i, :len(r)] = r
+    return tab, np.array([len(r) for r in rows], np.int32)
+
+
+def seq_ratio_tables(times):
+    """maxiRatioSeq::playTrig's boundary tables for a list of ratio lists (mxg_seq_ratio_host: host arithmetic, the reference's
+    operations in the reference's order).  Returns (norm [P][L], lengths [P])."""
+    tab, lens = seq_table(times)
+    norm = np.zeros_like(tab)
+    check(lib().mxg_seq_ratio_host(tab.shape[0], tab.shape[1], lens.ctypes.data, tab.ctypes.data, norm.ctypes.data), "mxg_seq_ratio_host")
+    return norm, lens
+
+
+class _SeqTables:
+    """Value lists on the device: `values` = a list of lists; a voice picks its list with `select`."""
+
+    def _set_values(self, values):
+        if values is None:
+            self.values = self.vlen = None
+            self.values_shape = (0, 0)
+            return
+        tab, lens = seq_table(values)
+        self.values, self.vlen, self.values_shape = DeviceBuffer.from_numpy(tab), DeviceBuffer.from_numpy(lens), tab.shape
+
+    def _select(self, sel):
+        return None if sel is None else DeviceBuffer.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(sel, np.int32), (self.V,))))
+
+
+class maxiSeqBank(_Bank, _SeqTables):
+    """V fused sequencers (kernel K15, mxg_seq_render): a clock per voice -> maxiRatioSeq::playTrig against the voice's ratio
+    pattern -> playValues or maxiStep::pull over the voice's value list -> maxiZXToPulse::play.  `times` is a list of ratio lists
+    (at most 64 ratios each), `values` a list of value lists; setPattern / setValueList pick one per voice (default: list 0).
+    Patterns and lists are block-constant: change them between renders (setTimes / setValues).  The blocks render() returns stay
+    on the device and are what maxiEnvGenBank.play (trigger, gate) and maxiOscBank.render(per_sample=True) (value) accept."""
+
+    def __init__(self, voices, times=((1,),), values=None, stream=None):
+        super().__init__(voices, stream)
+        self.clock = DeviceBuffer(self.V)  # maxiOsc::phase of the internal clock
+        d = np.zeros((5, self.V))
+        d[[1, 3]] = 1.0                     # maxiTrigger::previousValue of maxiStep and maxiZXToPulse (H:594)
+        i = np.zeros((6, self.V), np.int64)
+        i[[0, 3, 4, 5]] = 1                 # maxiRatioSeq::first, the two firstTrigger, maxiStep::first
+        self.dstate, self.istate = DeviceBuffer.from_numpy(d), DeviceBuffer.from_numpy(i)
+        self.pattern = self.value_list = self.step = self.hold = None
+        self.setTimes(times)
+        self._set_values(values)
+
+    def setTimes(self, times):
+        norm, lens = seq_ratio_tables(times)
+        self.host_norm = norm
+        self.norm, self.len = DeviceBuffer.from_numpy(norm), DeviceBuffer.from_numpy(lens)
+
+    def setValues(self, values): self._set_values(values)
+    def setPattern(self, sel): self.pattern = self._select(sel)
+    def setValueList(self, sel): self.value_list = self._select(sel)
+    def setStep(self, step): self.step = _as_dev(step, self.V)
+    def setHold(self, samples): self.hold = _as_dev(samples, self.V)
+
+    def render(self, N, freq=None, phase=None, trig=True, val=None, gate=False):
+        """freq [V]: the internal clock maxiOsc::phasor(freq[v]); or phase: a device / numpy phase signal [N][V] or shared [N].
+        val: None, "values" (playValues) or "step" (maxiStep::pull).  Returns (trig, val, gate) device blocks [N][V], None where
+        not asked for; a stage that is not asked for does not run."""
+        if (freq is None) == (phase is None):
+            raise ValueError("give freq (internal clock) or phase (external), not both")
+        if val not in (None, "values", "step"):
+            raise ValueError("val must be None, 'values' or 'step'")
+        if val is not None and self.values is None:
+            raise ValueError("no value lists: pass values= or call setValues")
+        f = ph = None
+        pv = 0
+        if freq is not None:
+            f = _as_dev(freq, self.V)
+        else:
+            ph = phase if (isinstance(phase, DeviceBuffer) or hasattr(phase, "data_ptr")) else \
+                DeviceBuffer.from_numpy(np.ascontiguousarray(phase, np.float64))
+            pv = int(len(ph.shape) == 2)
+        outs = [DeviceBuffer((N, self.V), np.float64, zero=False) if w else None for w in (trig, val is not None, gate)]
+        check(lib().mxg_seq_render(self.V, N, _ptr(f), self.clock.ptr if f is not None else None, _ptr(ph), pv, self.norm.ptr, self.len.ptr,
+                                   self.host_norm.shape[0], self.host_norm.shape[1], _ptr(self.pattern), 1 if val == "step" else 0,
+                                   _ptr(self.values), _ptr(self.vlen), self.values_shape[0], self.values_shape[1], _ptr(self.value_list),
+                                   _ptr(self.step), _ptr(self.hold), self.dstate.ptr, self.istate.ptr, _ptr(outs[0]), _ptr(outs[1]),
+                                   _ptr(outs[2]), self.stream), "mxg_seq_render")
+        self._keep = (f, ph)
+        return tuple(outs)
+
+
+class _SeqSignalBank(_Bank, _SeqTables):
+    """One of the reference's sequencing classes driven by device signals [N][V] (mxg_seq_signal)."""
+    KIND = 0
+
+    def __init__(self, voices, values=None, stream=None):
+        super().__init__(voices, stream)
+        d, i = np.zeros((3, self.V)), np.zeros((2, self.V), np.int64)
+        self._fresh(d, i)
+        self.dstate, self.istate = DeviceBuffer.from_numpy(d), DeviceBuffer.from_numpy(i)
+        self.value_list = None
+        self._set_values(values)
+
+    def _fresh(self, d, i):
+        d[0] = 1.0  # maxiTrigger::previousValue
+        i[0] = 1    # firstTrigger
+
+    def setValues(self, values): self._set_values(values)
+    def setValueList(self, sel): self.value_list = self._select(sel)
+
+    def _dev(self, x, N):
+        if x is None or isinstance(x, DeviceBuffer) or hasattr(x, "data_ptr"):
+            return x
+        return DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float64).reshape(N, self.V))
+
+    def _run(self, a, b=None, par=None, out=None):
+        N = a.shape[0] if hasattr(a, "shape") else len(a)
+        a, b = self._dev(a, N), self._dev(b, N)
+        par = None if par is None else _as_dev(par, self.V)
+        out = self._out(N, out)
+        check(lib().mxg_seq_signal(self.KIND, self.V, N, _ptr(a), _ptr(b), _ptr(self.values), _ptr(self.vlen), self.values_shape[0],
+                                   self.values_shape[1], _ptr(self.value_list), _ptr(par), self.dstate.ptr, self.istate.ptr, _ptr(out),
+                                   self.stream), "mxg_seq_signal")
+        self._keep = (a, b, par)
+        return out
+
+
+class maxiTriggerBank(_SeqSignalBank):
+    """V x maxiTrigger (H:564-596)."""
+    KIND = 0
+
+    def onZX(self, input, out=None): return self._run(input, out=out)
+
+
+class maxiCounterBank(_SeqSignalBank):
+    """V x maxiCounter (H:1953-1977)."""
+    KIND = 1
+
+    def _fresh(self, d, i):
+        d[1:3] = 1.0
+        i[:] = 1
+
+    def count(self, incTrigger, resetTrigger, out=None): return self._run(incTrigger, resetTrigger, out=out)
+
+
+class maxiStepBank(_SeqSignalBank):
+    """V x maxiStep (H:2093-2141) over the value lists of the bank."""
+    KIND = 2
+
+    def _fresh(self, d, i):
+        d[0] = 1.0
+        i[:] = 1  # trig.firstTrigger, first
+
+    def pull(self, trigSig, step=1.0, out=None): return self._run(trigSig, par=step, out=out)
+
+
+class maxiIndexBank(_SeqSignalBank):
+    """V x maxiIndex (H:1982-2013) over the value lists of the bank."""
+    KIND = 3
+
+    def pull(self, trigSig, indexSig, out=None): return self._run(trigSig, indexSig, out=out)
+
+
+class maxiZXToPulseBank(_SeqSignalBank):
+    """V x maxiZXToPulse (H:2235-2262)."""
+    KIND = 4
+
+    def play(self, input, holdTimeInSamples, out=None): return self._run(input, par=holdTimeInSamples, out=out)
+
+
 class maxiSampleBank(_Bank):
     """V play heads over one maxiSample (H:602-783): the bank shares the sample data the way
     maxiGrains alias one maxiSample (L/maxiGrains.h:162)."""
