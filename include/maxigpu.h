@@ -599,6 +599,48 @@ int mxg_seq_signal(int kind, size_t V, size_t N, const double *d_in, const doubl
                    const int32_t *d_vlen, size_t PV, size_t LV, const int32_t *d_vpat, const double *d_par, double *d_dst,
                    int64_t *d_ist, double *d_out, void *stream);
 
+/* ---- analysis: maxiZeroCrossingDetector / maxiZeroCrossingRate / maxiEnvelopeFollower / maxiSampleAndHold (K16) ------
+ * (H:969-1040, 1214-1250.)  Compares, + - *, integer counts and indexing only: every output and every state array is
+ * BIT-EXACT.  Two defined departures: a window above cap is held at cap and counted in d_overflow, where the reference indexes
+ * out of bounds; the crossing count is a signed 64-bit integer, where the reference's size_t would pass through a negative
+ * double when the window changes over a filled ring.  A negative or NaN hold time (undefined in the reference) is 0 samples.
+ *
+ * mxg_analysis_render, one fused pass over d_in [N][V]; `want` is a non-empty set of MXG_ANA_WANT_* bits, per voice and sample:
+ *     zx   = maxiZeroCrossingDetector::zx(x): (prev <= 0 && x > 0), prev = x; 0.0 / 1.0              -> d_zx      [N][V]
+ *     zcr  = maxiZeroCrossingRate::play(x): push zx, count += zx, count -= tail(d_window[v])         -> d_zcr     [N][V]
+ *     env  = maxiEnvelopeFollower::play(x): a = fabs(x); env = (a > env ? attack : release) * (env - a) + a -> d_env_out [N][V]
+ *     sah  = maxiSampleAndHold::sah(x, ms), hold = (double)(size_t)(ms / 1000 * sampleRate) per sample -> d_sah   [N][V]
+ * A stage that is not wanted does not run: its state, parameter and output pointers are not read and may be NULL.  zx and zcr
+ * share one detector (d_prev_x); zx alone needs only d_prev_x.  The outputs are distinct from d_in and from each other; they are
+ * what mxg_envgen_render (tpv = 1), mxg_seq_signal and mxg_dynamics_render (d_control) read.
+ * State, in/out (fresh objects: all zero):
+ *     d_prev_x [V]                    the detector's previous_x
+ *     d_zring  u64 [ceil(cap/64)][V]  the ring of crossings, one BIT per slot, word-major: slot s is bit s & 63 of word s >> 6 of
+ *                                     the voice's column; the last word is partial when cap % 64 != 0 (its upper bits are unused)
+ *     d_zpos   i32 [V]                maxiRingBuf::idx; a stored position outside [0, cap) restarts at slot 0
+ *     d_zcount i64 [V]                runningCount
+ *     d_overflow u32 [V] (optional)   INCREASED by one per call for a voice whose window is above cap
+ *     d_env [V]; d_sah_phase, d_sah_value [V]
+ * Parameters: d_window u32 [V] in samples (the reference reads maxiSettings::sampleRate at play time against a ring sized at
+ * construction; 0 is the caller's error -- mxg_analysis_window_host refuses it, the kernel stays inside the ring);
+ * d_attack, d_release [V] from mxg_envfollow_coeff_host; d_hold_ms [V], or [N][V] with hold_per_sample = 1.  The sample rate of
+ * the hold time is read at the call (mxg_settings).
+ * mxg_envfollow_coeff_host: pow(0.01, 1.0 / (ms * sample_rate * 0.001)) with the host libm, the reference's own expression
+ * (setAttack / setRelease, H:1224-1231) -- the policy of the filter coefficients.
+ * mxg_analysis_window_host: the host check of h_window [V] before upload: refuses cap == 0 and a window of 0. */
+#define MXG_ANA_WANT_ZX 1
+#define MXG_ANA_WANT_ZCR 2
+#define MXG_ANA_WANT_ENV 4
+#define MXG_ANA_WANT_SAH 8
+#define MXG_ANA_WANT_ALL 15
+double mxg_envfollow_coeff_host(double ms, double sample_rate);
+int mxg_analysis_window_host(size_t V, const uint32_t *h_window, size_t cap);
+int mxg_analysis_render(size_t V, size_t N, const double *d_in, int want, double *d_prev_x, const uint32_t *d_window,
+                        uint64_t *d_zring, size_t cap, int32_t *d_zpos, int64_t *d_zcount, uint32_t *d_overflow,
+                        const double *d_attack, const double *d_release, double *d_env, const double *d_hold_ms,
+                        int hold_per_sample, double *d_sah_phase, double *d_sah_value, double *d_zx, double *d_zcr,
+                        double *d_env_out, double *d_sah, void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

@@ -1526,6 +1526,115 @@ private:
     double holdCounter = 0;
 };
 
+// ---- maxiSampleAndHold (H:969-991), maxiZeroCrossingDetector (H:996-1015), maxiZeroCrossingRate (H:1021-1040),
+// maxiEnvelopeFollowerType<T> (H:1214-1250), maxiPoll (H:2553-2573): the reference's time-domain analysis classes, host value
+// types like the sequencing helpers above (copyable; called once per sample between the unit generators).  The same arithmetic
+// as the banks' (maximilian_amd/csrc/mxg_analysis.h, kernel K16): compares, + - *, integer counts and indexing, the reference's
+// bits.  maxiZeroCrossingRate keeps its window of crossings one BIT per slot, sized from maxiSettings::sampleRate at
+// construction, and reads the window from the sample rate at each play().  Two defined departures: a window above the ring's
+// size complains once and is held at the size (the reference indexes out of bounds); the count is a signed 64-bit integer (the
+// reference's size_t would pass through a negative double when the window changes over a filled ring).  A negative or NaN hold
+// time is 0 samples (undefined in the reference).
+class maxiSampleAndHold {
+public:
+    inline double sah(double sigIn, double holdTimeMs) {  // H:973-985
+        const double t = holdTimeMs / 1000.0 * maxiSettings::sampleRate;
+        const double holdTimeSamples = t >= 1.0 ? std::trunc(t) : 0.0;  // (double)(size_t)t
+        if (phase >= holdTimeSamples) phase -= holdTimeSamples;
+        if (phase < 1.0) holdValue = sigIn;
+        phase++;
+        return holdValue;
+    }
+
+private:
+    double phase = 0;
+    double holdValue = 0;
+};
+
+class maxiZeroCrossingDetector {
+public:
+    inline bool zx(double x) {  // H:1002-1011
+        const bool res = previous_x <= 0 && x > 0;
+        previous_x = x;
+        return res;
+    }
+
+private:
+    double previous_x = 0;
+};
+
+class maxiZeroCrossingRate {
+public:
+    maxiZeroCrossingRate() : cap(maxiSettings::sampleRate ? maxiSettings::sampleRate : 1), bits((cap + 63) / 64, 0) {}  // C:1529-1531
+    double play(double signal) {  // H:1025-1034
+        size_t window = maxiSettings::sampleRate;
+        if (window > cap) {
+            maxigpu::ps::complain("maxiZeroCrossingRate: the sample rate is above the one the ring was sized from; the window is held at the ring's size");
+            window = cap;
+        }
+        if (window == 0) window = cap;
+        const bool bit = zxd.zx(signal);
+        const uint64_t m = (uint64_t)1 << (idx & 63);
+        uint64_t &w = bits[idx >> 6];
+        w = bit ? (w | m) : (w & ~m);
+        idx++;
+        if (idx == cap) idx = 0;
+        if (bit) runningCount++;
+        const size_t t = idx >= window ? idx - window : cap - (window - idx);  // maxiRingBuf::tail, after the push
+        runningCount -= (long long)((bits[t >> 6] >> (t & 63)) & 1);
+        return (double)runningCount;
+    }
+
+private:
+    size_t cap;
+    std::vector<uint64_t> bits;
+    size_t idx = 0;
+    long long runningCount = 0;
+    maxiZeroCrossingDetector zxd;
+};
+
+template <typename T>
+class maxiEnvelopeFollowerType {
+public:
+    maxiEnvelopeFollowerType() {
+        setAttack(100);
+        setRelease(100);
+        env = 0;
+    }
+    // the reference's expression in the reference's types, host libm (T = double: what mxg_envfollow_coeff_host returns)
+    void setAttack(T attackMS) { attack = pow(0.01, 1.0 / (attackMS * maxiSettings::sampleRate * 0.001)); }
+    void setRelease(T releaseMS) { release = pow(0.01, 1.0 / (releaseMS * maxiSettings::sampleRate * 0.001)); }
+    inline T play(T input) {  // H:1232-1240; T = float does its recurrence in float
+        input = fabs(input);
+        if (input > env) env = attack * (env - input) + input;
+        else env = release * (env - input) + input;
+        return env;
+    }
+    void reset() { env = 0; }
+    inline T getEnv() { return env; }
+    inline void setEnv(T val) { env = val; }
+
+private:
+    T attack, release, env;
+};
+typedef maxiEnvelopeFollowerType<double> maxiEnvelopeFollower;
+typedef maxiEnvelopeFollowerType<float> maxiEnvelopeFollowerF;
+
+class maxiPoll {
+public:
+    double poll(double val, double frequency = 4, string txt = "", string end = "\n") {  // H:2562-2570: LOG(x) is cout << x
+        if (imp.impulse(frequency)) {
+            cout << txt;
+            cout << val;
+            cout << end;
+        }
+        return val;
+    }
+
+private:
+    maxiOsc imp;
+};
+
 // ---- maxiSample (H:602-790; C:605-1075): the play family over a buffer uploaded once ---------------------------------
 // The buffer lives on the device.  The members that EDIT it (normalise, autoTrim, loopRecord) work on a host copy fetched on
 // first use and write back what they changed -- setup-time utilities of the reference, not the per-sample path -- with the

@@ -760,6 +760,73 @@ private:
     maxigpu::DeviceArray<uint32_t> ovf_, win_;
 };
 
+// ---- analysis (H:969-1040, 1214-1250; kernel K16): what makes a trigger, a level or a held value FROM the audio --------
+// V x (maxiZeroCrossingDetector, maxiZeroCrossingRate, maxiEnvelopeFollower, maxiSampleAndHold) over one input block [N][V]
+// (mxg_analysis_render).  An output whose pointer is null is not rendered and its stage's state is untouched.  `capacity` is the
+// size of the ring of crossings in samples (the reference sizes it from the sample rate at construction); the window defaults to
+// it, the follower to setAttack(100), setRelease(100) at the sample rate in force at construction.  The ring holds one bit per
+// slot: u64 [ceil(capacity / 64)][V].
+class maxiAnalysisBank {
+public:
+    maxiAnalysisBank(size_t voices, size_t capacity = maxiSettings::sampleRate) : V(voices), cap(capacity) {
+        if (cap < 1) throw std::runtime_error("maxiAnalysisBank: the ring needs at least one slot");
+        window.assign(V, (uint32_t)cap);
+        win_.upload(window);
+        const double c = mxg_envfollow_coeff_host(100.0, (double)maxiSettings::sampleRate);
+        attack_.upload(std::vector<double>(V, c));
+        release_.upload(std::vector<double>(V, c));
+        hold_.resize(V);
+        reset();
+    }
+    void reset() {  // fresh objects: everything zero (the window, the coefficients and the hold times stay)
+        prev_.resize(V); ring_.resize(((cap + 63) / 64) * V); pos_.resize(V); count_.resize(V); ovf_.resize(V);
+        env_.resize(V); phase_.resize(V); value_.resize(V);
+    }
+    void setWindow(const std::vector<uint32_t> &samples) {  // per voice; 0 is refused, above the capacity: held there and counted
+        if (samples.size() != V) throw std::runtime_error("maxiAnalysisBank::setWindow: one window per voice");
+        maxigpu::check(mxg_analysis_window_host(V, samples.data(), cap), "mxg_analysis_window_host");
+        window = samples;
+        win_.upload(window);
+    }
+    void setWindow(uint32_t samples) { setWindow(std::vector<uint32_t>(V, samples)); }
+    void setAttack(double ms) { attack_.upload(std::vector<double>(V, mxg_envfollow_coeff_host(ms, (double)maxiSettings::sampleRate))); }
+    void setRelease(double ms) { release_.upload(std::vector<double>(V, mxg_envfollow_coeff_host(ms, (double)maxiSettings::sampleRate))); }
+    void setHold(const std::vector<double> &ms) {
+        if (ms.size() != V) throw std::runtime_error("maxiAnalysisBank::setHold: one hold time per voice");
+        hold_.upload(ms);
+    }
+    void setHold(double ms) { setHold(std::vector<double>(V, ms)); }
+    // d_hold_ms: null = the bank's per-voice hold times, else a hold time per sample [N][V]
+    void render(size_t N, const double *d_in, double *d_zx, double *d_zcr, double *d_env, double *d_sah, const double *d_hold_ms = nullptr,
+                void *stream = nullptr) {
+        const int want = (d_zx ? MXG_ANA_WANT_ZX : 0) | (d_zcr ? MXG_ANA_WANT_ZCR : 0) | (d_env ? MXG_ANA_WANT_ENV : 0) |
+                         (d_sah ? MXG_ANA_WANT_SAH : 0);
+        maxigpu::check(mxg_analysis_render(V, N, d_in, want, prev_.get(), win_.get(), ring_.get(), cap, pos_.get(), count_.get(), ovf_.get(),
+                                           attack_.get(), release_.get(), env_.get(), d_hold_ms ? d_hold_ms : hold_.get(), d_hold_ms ? 1 : 0,
+                                           phase_.get(), value_.get(), d_zx, d_zcr, d_env, d_sah, stream), "mxg_analysis_render");
+    }
+    size_t voices() const { return V; }
+    size_t capacity() const { return cap; }
+    // state arrays on the device (include/maxigpu.h)
+    double *previousX() { return prev_.get(); }
+    uint64_t *ring() { return ring_.get(); }
+    int32_t *ringPosition() { return pos_.get(); }
+    int64_t *runningCount() { return count_.get(); }
+    uint32_t *overflow() { return ovf_.get(); }
+    double *envelope() { return env_.get(); }
+    double *holdPhase() { return phase_.get(); }
+    double *holdValue() { return value_.get(); }
+    std::vector<uint32_t> window;  // host copy, in samples
+
+private:
+    size_t V, cap;
+    maxigpu::DeviceArray<double> prev_, env_, phase_, value_, attack_, release_, hold_;
+    maxigpu::DeviceArray<uint64_t> ring_;
+    maxigpu::DeviceArray<int32_t> pos_;
+    maxigpu::DeviceArray<int64_t> count_;
+    maxigpu::DeviceArray<uint32_t> ovf_, win_;
+};
+
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
 namespace maxigpu {
 // lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device

@@ -116,6 +116,10 @@ SIGNATURES = {
     "mxg_seq_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                c_int, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 9),
     "mxg_seq_signal": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 6),
+    "mxg_envfollow_coeff_host": (c_double, [c_double, c_double]),
+    "mxg_analysis_window_host": (c_int, [c_size_t, c_void_p, c_size_t]),
+    "mxg_analysis_render": (c_int, [c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t] + [c_void_p] * 7 +
+                            [c_int] + [c_void_p] * 7),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

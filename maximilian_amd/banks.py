@@ -1122,6 +1122,102 @@ class maxiRMSBank(_Bank):
         return out
 
 
+ANALYSIS_WANT = {"zx": 1, "zcr": 2, "env": 4, "sah": 8}
+
+
+def analysis_want(want):
+    """Names ('zx', 'zcr', 'env', 'sah'), an iterable of them or MXG_ANA_WANT_* bits -> the bits."""
+    if isinstance(want, (int, np.integer)):
+        return int(want)
+    names = [want] if isinstance(want, str) else list(want)
+    bad = [n for n in names if n not in ANALYSIS_WANT]
+    if bad:
+        raise ValueError("want: unknown output %r (one of %s)" % (bad[0], ", ".join(ANALYSIS_WANT)))
+    return sum(ANALYSIS_WANT[n] for n in set(names))
+
+
+def envfollow_coeff(ms, sample_rate=None):
+    """maxiEnvelopeFollower::setAttack / setRelease (H:1224-1231): pow(0.01, 1.0 / (ms * sampleRate * 0.001)), host libm."""
+    sr = float(maxiSettings.sampleRate if sample_rate is None else sample_rate)
+    f = lib().mxg_envfollow_coeff_host
+    return np.array([f(float(m), sr) for m in np.atleast_1d(np.asarray(ms, np.float64)).reshape(-1)]).reshape(np.shape(ms))
+
+
+class maxiAnalysisBank(_Bank):
+    """V x (maxiZeroCrossingDetector, maxiZeroCrossingRate, maxiEnvelopeFollower, maxiSampleAndHold) over one input block
+    (H:969-1040, 1214-1250; mxg_analysis_render, K16).  `cap` is the size of the ring of crossings in samples (None: the
+    sample rate in force now, as the reference's constructor sizes it).  The window defaults to `cap`; the follower to
+    setAttack(100), setRelease(100).  State: prev_x [V], zring u64 [ceil(cap/64)][V] (one bit per slot), zpos [V], zcount
+    [V], overflow [V], env [V], sah_phase [V], sah_value [V]."""
+
+    def __init__(self, voices, cap=None, stream=None):
+        super().__init__(voices, stream)
+        self.cap = int(maxiSettings.sampleRate if cap is None else cap)
+        if self.cap < 1:
+            raise ValueError("cap: the ring needs at least one slot")
+        self.window = np.full(self.V, self.cap, np.uint32)
+        self._dwin = None
+        self.attack = DeviceBuffer.from_numpy(np.full(self.V, envfollow_coeff(100.0)))
+        self.release = DeviceBuffer.from_numpy(np.full(self.V, envfollow_coeff(100.0)))
+        self.hold_ms = DeviceBuffer(self.V)
+        self.reset()
+
+    def reset(self):
+        """Fresh objects: everything zero (the window and the follower's coefficients stay)."""
+        V = self.V
+        self.prev_x = DeviceBuffer(V)
+        self.zring = DeviceBuffer(((self.cap + 63) // 64, V), np.uint64)
+        self.zpos = DeviceBuffer(V, np.int32)
+        self.zcount = DeviceBuffer(V, np.int64)
+        self.overflow = DeviceBuffer(V, np.uint32)
+        self.env = DeviceBuffer(V)
+        self.sah_phase = DeviceBuffer(V)
+        self.sah_value = DeviceBuffer(V)
+
+    def setWindow(self, samples):
+        """The rate's window in samples, scalar or [V] (the reference: maxiSettings::sampleRate at play time).  0 is refused;
+        above cap it is held at cap by the kernel and counted in `overflow`."""
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, np.uint32), (self.V,)))
+        check(lib().mxg_analysis_window_host(self.V, w.ctypes.data, self.cap), "mxg_analysis_window_host")
+        self.window = w.copy()
+        self._dwin = None
+
+    def setAttack(self, attackMS):
+        self.attack = DeviceBuffer.from_numpy(np.broadcast_to(envfollow_coeff(attackMS), (self.V,)))
+
+    def setRelease(self, releaseMS):
+        self.release = DeviceBuffer.from_numpy(np.broadcast_to(envfollow_coeff(releaseMS), (self.V,)))
+
+    def render(self, x, want=("zx", "zcr", "env", "sah"), hold_ms=None, out=None):
+        """x: device [N][V].  hold_ms: scalar / [V], or a device or host [N][V] array (a hold time per sample); None keeps the
+        last one.  Returns {name: [N][V] device block} for the requested outputs; `out` may supply some of them."""
+        bits = analysis_want(want)
+        N = x.shape[0]
+        _fx_dev(x, np.float64, "input", (N * self.V,))
+        per_sample = 0
+        hold = self.hold_ms
+        if hold_ms is not None:
+            if isinstance(hold_ms, DeviceBuffer) or hasattr(hold_ms, "data_ptr"):
+                per_sample = 1 if _fx_dev(hold_ms, np.float64, "hold_ms", (self.V, N * self.V)) == N * self.V else 0
+                hold = hold_ms
+            else:
+                a = np.asarray(hold_ms, np.float64)
+                if a.ndim == 2:
+                    hold, per_sample = DeviceBuffer.from_numpy(a.reshape(N, self.V)), 1
+                else:
+                    hold = self.hold_ms = DeviceBuffer.from_numpy(np.broadcast_to(a, (self.V,)))
+        if self._dwin is None:
+            self._dwin = DeviceBuffer.from_numpy(self.window)
+        out = dict(out or {})
+        res = {n: out[n] if n in out else DeviceBuffer((N, self.V), np.float64, zero=False) for n, b in ANALYSIS_WANT.items() if bits & b}
+        check(lib().mxg_analysis_render(self.V, N, _ptr(x), bits, self.prev_x.ptr, self._dwin.ptr, self.zring.ptr, self.cap,
+                                        self.zpos.ptr, self.zcount.ptr, self.overflow.ptr, self.attack.ptr, self.release.ptr,
+                                        self.env.ptr, _ptr(hold), per_sample, self.sah_phase.ptr, self.sah_value.ptr,
+                                        _ptr(res.get("zx")), _ptr(res.get("zcr")), _ptr(res.get("env")), _ptr(res.get("sah")),
+                                        self.stream), "mxg_analysis_render")
+        return res
+
+
 SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAtSpeed": 4,
                 "playOnceAtSpeed": 5, "playUntilAtSpeed": 6, "play4": 7, "playAtSpeedBetweenPoints": 8,
                 # trigger-driven (mxg_sample_render_trig)
