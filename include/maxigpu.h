@@ -641,6 +641,40 @@ int mxg_analysis_render(size_t V, size_t N, const double *d_in, int want, double
                         int hold_per_sample, double *d_sah_phase, double *d_sah_value, double *d_zx, double *d_zcr,
                         double *d_env_out, double *d_sah, void *stream);
 
+/* ---- maxiKuramotoOscillatorSet / maxiAsyncKuramotoOscillator (K17) ------------------------------------------------------
+ * (H:1628-1808.)  S sets of N phase-coupled oscillators (N = 1 .. 64; 0 and more than 64 are refused without a launch), B
+ * samples per call.  Per set and sample, as maxiKuramotoOscillatorSet::play(freq, K):
+ *     gathered[j] = phase[j] for all j;  then for every oscillator i, in order,
+ *     adj = sum over j, in order, of sin(gathered[j] - phase[i]);
+ *     phase[i] += dt * (freq + ((K / (double)N) * adj));  one wrap into [0, TWOPI);
+ *     mix = (sum of the new phases in i order) / (double)N.
+ * dt = TWOPI / sampleRate, read at the call (mxg_settings).  Everything but the sine keeps the reference's expression trees; the
+ * sine is the library's own (within 1 ULP of glibc's per term), so phases and mix stay within the reference's own accumulated
+ * rounding -- and are bit-identical to the host build of maximilian_amd/csrc/mxg_kuramoto.h.
+ * mode bits:
+ *     MXG_KURA_MEANFIELD  a TOLERANCE mode: adj = cos(phase[i]) * S - sin(phase[i]) * C with S = sum_j sin(gathered[j]),
+ *                         C = sum_j cos(gathered[j]) in j order -- N sine / cosine pairs per sample instead of N * N sines
+ *     MXG_KURA_ASYNC      maxiAsyncKuramotoOscillator: d_gathered is refreshed from the phases, and K applied, only on the first
+ *                         sample of a call whose d_update[s] is non-zero; the kernel clears the flag.  Every other sample plays
+ *                         K = 0 on the stale gathered phases.  (The sum is left out where that provably changes nothing: all
+ *                         phases of the wavefront's sets within |32| and freq not -0.0; a non-finite phase propagates as in the
+ *                         reference.)
+ * d_freq, d_K: one value per set [S], or with freq_per_sample / K_per_sample a block [B][S] (what the other banks write).
+ * State, in/out: d_phase [S][N] (set-major); async only: d_gathered [S][N], d_update i32 [S] (both may be NULL otherwise).
+ * The reference's setPhase / setPhases between two calls is a write to d_phase (and, async, raising d_update[s]).
+ * Outputs, any subset chosen by `want` (an unwanted block is not written and may be NULL; want = 0 only advances the state):
+ *     MXG_KURA_WANT_MIX     d_mix        [B][S]      what play() returns
+ *     MXG_KURA_WANT_PHASES  d_phases_out [B][S][N]   what getPhase(i) returns after each sample
+ * Phases beyond |32| (the caller's setPhase; the wrap is applied once per sample) take the platform's sine above |x| = 64: still
+ * within 1 ULP per term, no longer bit-identical to the host build. */
+#define MXG_KURA_MEANFIELD 1
+#define MXG_KURA_ASYNC 2
+#define MXG_KURA_WANT_MIX 1
+#define MXG_KURA_WANT_PHASES 2
+int mxg_kuramoto_render(int mode, size_t S, size_t N, size_t B, const double *d_freq, int freq_per_sample, const double *d_K,
+                        int K_per_sample, double *d_phase, double *d_gathered, int32_t *d_update, int want, double *d_mix,
+                        double *d_phases_out, void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

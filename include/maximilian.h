@@ -1635,6 +1635,85 @@ private:
     maxiOsc imp;
 };
 
+// ---- maxiKuramotoOscillator (H:1628-1663), maxiKuramotoOscillatorSet (H:1668-1732), maxiAsyncKuramotoOscillator
+// (H:1740-1808): phase-coupled oscillators, host value types like the analysis classes above.  One set is N * N sines per sample
+// and is called between the unit generators, so the classes restate the reference's arithmetic with std::sin: linked against the
+// same libm they give the reference's bits.  Banks of many sets run on the device (maxiKuramotoBank in maximilian_bank.hpp,
+// mxg_kuramoto_render, kernel K17: the same expressions with the library's own sine, within the reference's own rounding).
+// Every oscillator of a set reads the phases gathered BEFORE any of them moved; the wrap is applied once; dt is taken from
+// maxiSettings::sampleRate when the oscillator is constructed.
+class maxiKuramotoOscillator {
+public:
+    maxiKuramotoOscillator() {}
+    inline double play(double freq, double K, std::vector<double> phases) {  // H:1640-1654 (the vector by value, as there)
+        double phaseAdj = 0;
+        for (size_t j = 0; j < phases.size(); j++) phaseAdj += std::sin(phases[j] - phase);
+        phase += dt * (freq + ((K / phases.size()) * phaseAdj));
+        if (phase >= TWOPI) phase -= TWOPI;
+        else if (phase < 0) phase += TWOPI;
+        return phase;
+    }
+    inline void setPhase(double newPhase) { phase = newPhase; }
+    inline double getPhase() { return phase; }
+
+private:
+    double phase = 0.0;
+    double dt = TWOPI / maxiSettings::sampleRate;
+};
+
+class maxiKuramotoOscillatorSet {
+public:
+    maxiKuramotoOscillatorSet(const size_t N) {
+        oscs.resize(N);
+        phases.resize(N);
+    }
+    void setPhases(const std::vector<double> &phases) {  // (one per oscillator, in order)
+        for (size_t i = 0; i < phases.size(); i++) oscs[i].setPhase(phases[i]);
+    }
+    void setPhase(const double phase, const size_t oscillatorIdx) { oscs[oscillatorIdx].setPhase(phase); }
+    double getPhase(size_t i) { return oscs[i].getPhase(); }
+    size_t size() { return oscs.size(); }
+    double play(double freq, double K) {  // H:1714-1727
+        for (size_t i = 0; i < phases.size(); i++) phases[i] = oscs[i].getPhase();
+        double mix = 0.0;
+        for (size_t i = 0; i < oscs.size(); i++) mix += oscs[i].play(freq, K, phases);
+        return mix / phases.size();
+    }
+
+protected:
+    std::vector<maxiKuramotoOscillator> oscs;
+    std::vector<double> phases;
+};
+
+// The set with asynchronous updates: the gathered phases are refreshed, and K applied, only on the play() after a setPhase /
+// setPhases; otherwise the oscillators run free on the stale phases with K = 0 (the sum is still formed: a non-finite phase
+// propagates through 0 * adj, as in the reference).
+class maxiAsyncKuramotoOscillator : public maxiKuramotoOscillatorSet {
+public:
+    maxiAsyncKuramotoOscillator(const size_t N) : maxiKuramotoOscillatorSet(N) {}
+    void setPhase(const double phase, const size_t oscillatorIdx) {
+        maxiKuramotoOscillatorSet::setPhase(phase, oscillatorIdx);
+        update = 1;
+    }
+    void setPhases(const std::vector<double> &phases) {
+        maxiKuramotoOscillatorSet::setPhases(phases);
+        update = 1;
+    }
+    double play(double freq, double K) {  // H:1775-1792
+        if (update)
+            for (size_t i = 0; i < phases.size(); i++) phases[i] = oscs[i].getPhase();
+        double mix = 0.0;
+        for (size_t i = 0; i < oscs.size(); i++) mix += oscs[i].play(freq, update ? K : 0, phases);
+        update = 0;
+        return mix / phases.size();
+    }
+    double getPhase(size_t i) { return maxiKuramotoOscillatorSet::getPhase(i); }
+    size_t size() { return maxiKuramotoOscillatorSet::size(); }
+
+private:
+    bool update = 0;
+};
+
 // ---- maxiSample (H:602-790; C:605-1075): the play family over a buffer uploaded once ---------------------------------
 // The buffer lives on the device.  The members that EDIT it (normalise, autoTrim, loopRecord) work on a host copy fetched on
 // first use and write back what they changed -- setup-time utilities of the reference, not the per-sample path -- with the

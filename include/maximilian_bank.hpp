@@ -827,6 +827,76 @@ private:
     maxigpu::DeviceArray<uint32_t> ovf_, win_;
 };
 
+// ---- phase-coupled oscillator sets (H:1628-1808; kernel K17) ---------------------------------------------------------
+// S x maxiKuramotoOscillatorSet -- asynchronous: maxiAsyncKuramotoOscillator -- of N = 1 .. 64 oscillators each
+// (mxg_kuramoto_render).  play() is the reference's play(freq, K) for B samples: the mix block [B][S], and on request what
+// getPhase(i) returns after each sample [B][S][N].  freq and K are one value per set, or device blocks [B][S] written by the
+// other banks.  setPhase / setPhases act between two blocks, as the reference's do between two samples; on asynchronous sets
+// they raise the set's flag, which the next play() consumes on its first sample.  meanfield: the tolerance mode that forms the
+// coupling sum from the set's summed sines and cosines (N pairs per sample instead of N * N sines).
+class maxiKuramotoBank {
+public:
+    maxiKuramotoBank(size_t sets, size_t N, bool meanfield = false, bool asynchronous = false)
+        : S(sets), N_(N), mode((meanfield ? MXG_KURA_MEANFIELD : 0) | (asynchronous ? MXG_KURA_ASYNC : 0)) {
+        if (N_ < 1 || N_ > 64) throw std::runtime_error("maxiKuramotoBank: a set has 1 .. 64 oscillators");
+        freq_.resize(S);
+        K_.resize(S);
+        reset();
+    }
+    void reset() {  // fresh sets: phases 0, gathered phases 0, flags down
+        phase_.resize(S * N_);
+        if (mode & MXG_KURA_ASYNC) { gathered_.resize(S * N_); update_.resize(S); }
+    }
+    size_t sets() const { return S; }
+    size_t size() const { return N_; }
+    void setFreq(const std::vector<double> &f) { per_set(f, freq_, "setFreq"); }
+    void setFreq(double f) { setFreq(std::vector<double>(S, f)); }
+    void setK(const std::vector<double> &k) { per_set(k, K_, "setK"); }
+    void setK(double k) { setK(std::vector<double>(S, k)); }
+    // [S][N], set-major
+    void setPhases(const std::vector<double> &phases) {
+        if (phases.size() != S * N_) throw std::runtime_error("maxiKuramotoBank::setPhases: S * N phases");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        phase_.upload(phases);
+        if (mode & MXG_KURA_ASYNC) update_.upload(std::vector<int32_t>(S, 1));
+    }
+    void setPhase(double phase, size_t oscillatorIdx, size_t set) {
+        if (set >= S || oscillatorIdx >= N_) throw std::runtime_error("maxiKuramotoBank::setPhase: no such oscillator");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        phase_.upload(&phase, 1, set * N_ + oscillatorIdx);
+        const int32_t one = 1;
+        if (mode & MXG_KURA_ASYNC) update_.upload(&one, 1, set);
+    }
+    std::vector<double> phases() const {  // getPhase(i) of every set, [S][N]
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        return phase_.download();
+    }
+    // d_mix [B][S] and / or d_phases_out [B][S][N] (null: not rendered); d_freq / d_K: null = the bank's per-set values, else a
+    // block [B][S]
+    void play(size_t B, double *d_mix, double *d_phases_out = nullptr, const double *d_freq = nullptr, const double *d_K = nullptr,
+              void *stream = nullptr) {
+        const int want = (d_mix ? MXG_KURA_WANT_MIX : 0) | (d_phases_out ? MXG_KURA_WANT_PHASES : 0);
+        maxigpu::check(mxg_kuramoto_render(mode, S, N_, B, d_freq ? d_freq : freq_.get(), d_freq ? 1 : 0, d_K ? d_K : K_.get(), d_K ? 1 : 0,
+                                           phase_.get(), gathered_.get(), update_.get(), want, d_mix, d_phases_out, stream),
+                       "mxg_kuramoto_render");
+    }
+    // state arrays on the device (include/maxigpu.h)
+    double *phase() { return phase_.get(); }
+    double *gathered() { return gathered_.get(); }
+    int32_t *update() { return update_.get(); }
+
+private:
+    void per_set(const std::vector<double> &v, maxigpu::DeviceArray<double> &d, const char *what) {
+        if (v.size() != S) throw std::runtime_error(std::string("maxiKuramotoBank::") + what + ": one value per set");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d.upload(v);
+    }
+    size_t S, N_;
+    int mode;
+    maxigpu::DeviceArray<double> freq_, K_, phase_, gathered_;
+    maxigpu::DeviceArray<int32_t> update_;
+};
+
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
 namespace maxigpu {
 // lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device

@@ -120,6 +120,8 @@ SIGNATURES = {
     "mxg_analysis_window_host": (c_int, [c_size_t, c_void_p, c_size_t]),
     "mxg_analysis_render": (c_int, [c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t] + [c_void_p] * 7 +
                             [c_int] + [c_void_p] * 7),
+    "mxg_kuramoto_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                            c_int, c_void_p, c_void_p, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

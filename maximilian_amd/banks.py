@@ -1218,6 +1218,114 @@ class maxiAnalysisBank(_Bank):
         return res
 
 
+KURAMOTO_WANT = {"mix": 1, "phases": 2}
+KURAMOTO_MAX_N = 64
+
+
+class maxiKuramotoBank(_Bank):
+    """S x maxiKuramotoOscillatorSet (asynchronous=True: maxiAsyncKuramotoOscillator) of N = 1 .. 64 phase-coupled oscillators
+    each (H:1628-1808; mxg_kuramoto_render, K17).  meanfield=True selects the tolerance mode that forms the coupling sum from
+    the set's summed sines and cosines (N pairs per sample instead of N * N sines).  State: phase [S][N]; asynchronous sets
+    also gathered [S][N] and update i32 [S].  dt is TWOPI / maxiSettings.sampleRate at each call.  set_phase / set_phases are
+    the reference's setPhase / setPhases between two blocks; on asynchronous sets they raise the set's flag."""
+
+    def __init__(self, sets, N, meanfield=False, asynchronous=False, stream=None):
+        self.S, self.N = int(sets), int(N)
+        if not 1 <= self.N <= KURAMOTO_MAX_N:   # (before the device is touched, as the entry point refuses it)
+            raise ValueError("N: a set has 1 .. %d oscillators, got %d" % (KURAMOTO_MAX_N, self.N))
+        super().__init__(sets, stream)
+        self.mode = (1 if meanfield else 0) | (2 if asynchronous else 0)
+        self.asynchronous = bool(asynchronous)
+        self.freq = DeviceBuffer(self.S)
+        self.K = DeviceBuffer(self.S)
+        self.reset()
+
+    def reset(self):
+        """Fresh sets: phases 0, gathered phases 0, flags down."""
+        self.phase = DeviceBuffer((self.S, self.N))
+        self.gathered = DeviceBuffer((self.S, self.N)) if self.asynchronous else None
+        self.update = DeviceBuffer(self.S, np.int32) if self.asynchronous else None
+
+    def phases(self):
+        """getPhase(i) of every set: host [S][N]."""
+        return self.phase.numpy()
+
+    def set_phases(self, phases, sets=None):
+        """setPhases: [N] for every set, or [S][N]; `sets` restricts it to those sets (rows of `phases` then match them)."""
+        cur = self.phase.numpy()
+        idx = np.arange(self.S) if sets is None else np.atleast_1d(np.asarray(sets, np.int64))
+        cur[idx] = np.broadcast_to(np.asarray(phases, np.float64), (len(idx), self.N))
+        self.phase.upload(cur)
+        self._raise(idx)
+
+    def set_phase(self, phase, oscillatorIdx, sets=None):
+        """setPhase(phase, oscillatorIdx) on every set, or on `sets` (phase: scalar or one per set)."""
+        if not 0 <= int(oscillatorIdx) < self.N:
+            raise IndexError("oscillatorIdx %d outside a set of %d" % (oscillatorIdx, self.N))
+        cur = self.phase.numpy()
+        idx = np.arange(self.S) if sets is None else np.atleast_1d(np.asarray(sets, np.int64))
+        cur[idx, int(oscillatorIdx)] = np.broadcast_to(np.asarray(phase, np.float64), (len(idx),))
+        self.phase.upload(cur)
+        self._raise(idx)
+
+    def _raise(self, idx):
+        if self.asynchronous:
+            up = self.update.numpy()
+            up[idx] = 1
+            self.update.upload(up)
+
+    def _param(self, x, B, keep, what):
+        """scalar / [S] (kept for the next call) or a device / host [B][S] block -> (buffer, per_sample)."""
+        if isinstance(x, DeviceBuffer) or hasattr(x, "data_ptr"):
+            n = _fx_dev(x, np.float64, what, (self.S, B * self.S))
+            return x, (1 if n == B * self.S and B > 1 else 0)   # (B == 1: [S] and [1][S] are the same memory)
+        a = np.asarray(x, np.float64)
+        if a.ndim == 2:
+            return DeviceBuffer.from_numpy(a.reshape(B, self.S)), 1
+        keep.upload(np.broadcast_to(a, (self.S,)))
+        return keep, 0
+
+    def render(self, B, freq, K, want=("mix",), out=None):
+        """B samples.  freq, K: scalar / [S], or a device or host [B][S] block (one value per sample).  Returns {name: device
+        block} for the wanted outputs: "mix" [B][S], "phases" [B][S][N]; `out` may supply them."""
+        names = [want] if isinstance(want, str) else list(want)
+        bad = [n for n in names if n not in KURAMOTO_WANT]
+        if bad:
+            raise ValueError("want: unknown output %r (one of %s)" % (bad[0], ", ".join(KURAMOTO_WANT)))
+        bits = sum(KURAMOTO_WANT[n] for n in set(names))
+        B = int(B)
+        f, fps = self._param(freq, B, self.freq, "freq")
+        k, kps = self._param(K, B, self.K, "K")
+        out = dict(out or {})
+        shapes = {"mix": (B, self.S), "phases": (B, self.S, self.N)}
+        res = {n: out[n] if n in out else DeviceBuffer(shapes[n], np.float64, zero=False) for n, b in KURAMOTO_WANT.items() if bits & b}
+        check(lib().mxg_kuramoto_render(self.mode, self.S, self.N, B, _ptr(f), fps, _ptr(k), kps, self.phase.ptr, _ptr(self.gathered),
+                                        _ptr(self.update), bits, _ptr(res.get("mix")), _ptr(res.get("phases")), self.stream),
+              "mxg_kuramoto_render")
+        return res
+
+    def play(self, freq, K, B=None, out=None):
+        """play(freq, K) for B samples -> the mix block, device [B][S].  B defaults to the rows of a [B][S] freq or K."""
+        if B is None:
+            for x in (freq, K):
+                if len(getattr(x, "shape", ())) == 2:
+                    B = int(x.shape[0])
+            if B is None:
+                raise ValueError("play: B is needed when freq and K are per set")
+        return self.render(B, freq, K, ("mix",), None if out is None else {"mix": out})["mix"]
+
+    def render_phases(self, freq, K, B=None, out=None):
+        """As play(), returning (mix [B][S], phases [B][S][N])."""
+        if B is None:
+            for x in (freq, K):
+                if len(getattr(x, "shape", ())) == 2:
+                    B = int(x.shape[0])
+            if B is None:
+                raise ValueError("render_phases: B is needed when freq and K are per set")
+        r = self.render(B, freq, K, ("mix", "phases"), out)
+        return r["mix"], r["phases"]
+
+
 SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAtSpeed": 4,
                 "playOnceAtSpeed": 5, "playUntilAtSpeed": 6, "play4": 7, "playAtSpeedBetweenPoints": 8,
                 # trigger-driven (mxg_sample_render_trig)
