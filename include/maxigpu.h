@@ -675,6 +675,64 @@ int mxg_kuramoto_render(int mode, size_t S, size_t N, size_t B, const double *d_
                         int K_per_sample, double *d_phase, double *d_gathered, int32_t *d_update, int want, double *d_mix,
                         double *d_phases_out, void *stream);
 
+/* ---- shapers, cross-fade, select and line: maxiNonlinearity / maxiDistortion, maxiXFade, maxiSelect(X), maxiLine (K18) ----
+ * (H:1046-1139, 1491-1617, 2018-2088.)  All blocks are [N][V] doubles.  The first three are streams without a recurrence over
+ * time: flat over the N * V elements, 16-byte accesses where every pointer is 16-byte aligned (else, and with the knob rw_store
+ * = 1, 8-byte ones); a per-voice parameter [V] is read at element % V.
+ *
+ * mxg_shape_render: d_out[i] = maxiNonlinearity::<mode>(d_in[i], ...); d_out == d_in (in place) is allowed.
+ *     MXG_SHAPE_HARDCLIP, _FASTATAN                 no parameter (d_a, d_b may be NULL)                        BIT-EXACT
+ *     MXG_SHAPE_SOFTCLIP                            no parameter; the cube is (x * x) * x for the reference's pow(x, 3): at most
+ *                                                   2^-52 absolute from it, bit-identical to the host build of mxg_shaper.h
+ *     MXG_SHAPE_FASTATANDIST  d_a = shape                                                                      BIT-EXACT
+ *     MXG_SHAPE_ATANDIST      d_a = shape, d_b = 1.0 / atan(shape) from mxg_atan_norm_host (per voice only; with per_sample the
+ *                             factor is formed on the device and d_b is not read); the device's atan: tolerance, DESIGN.md
+ *     MXG_SHAPE_ASYMCLIP      d_a = a (the exponent of the NEGATIVE half, as the reference uses it), d_b = b; the device's pow:
+ *                             tolerance, DESIGN.md
+ * The clipped branches (|x| >= 1 gives exactly +-1) and NaN positions are the reference's in every mode.  per_sample = 0: d_a, d_b
+ * are [V]; 1: blocks [N][V] (K16's hold_per_sample convention).
+ * mxg_atan_norm_host: 1.0 / atan(shape) with the host libm, the reference's own expression (H:1128).
+ *
+ * mxg_xfade_render: maxiXFade::xfade over C = 1 .. 8 channels: d_ch1, d_ch2, d_out are [C][N][V]; d_xfader is [V], or [N][V] with
+ * xfader_per_sample.  n = linlin(clamp(x, -1, 1), -1, 1, 0, 1) in the reference's operation order, the gains sqrt(1.0 - n) and
+ * sqrt(n) are formed once per element and applied to all C channels: out = (ch1 * g1) + (ch2 * g2).  BIT-EXACT.  d_out may be
+ * d_ch1 or d_ch2.
+ *
+ * mxg_select_render: maxiSelect::play (interpolate = 0) / maxiSelectX::play (1) over K = 1 .. 64 values: d_index [N][V]; d_values
+ * [K][V] constants, or with values_are_signals [K][N][V].  normalised: index *= (K - 1e-9).  Below 0 -> 0, >= K -> K - 1.
+ * SelectX: a1 = floor(index), a2 = a1 + 1 wrapping to 0, mix = index - a1, (v[a1] * (1.0 - mix)) + (v[a2] * mix).  BIT-EXACT.
+ * One defined departure: a NaN index (undefined in the reference: it falls through both clamps into a cast) is taken as index
+ * 0.0 -- it reads element 0 -- and is counted per voice in d_nan_count u32 [V] when that is not NULL (INCREASED, never cleared).
+ *
+ * mxg_line_render: maxiLine::play per voice and sample; d_trig [N][V], or NULL: the constant trig_const on every sample
+ * (line.play(1)).  d_par [5][V] = lineStart, lineEnd, inc, oneShot, trigEnable (the last two: non-zero = true); d_st [4][V], in/out
+ * = lineValue, lastTrigVal, triggered, lineComplete (fresh objects: 0, -1, 0, 0; the flags are 0.0 / 1.0).  BIT-EXACT, the state
+ * included.  d_out is distinct from d_trig.  inc of +-Inf or NaN (a duration of 0) is not refused: the compares decide, as in
+ * the reference.
+ * mxg_line_prepare_host: maxiLine::prepare on HOST copies of d_par / d_st for the voices whose h_mask is non-zero (NULL: all):
+ * lineValue takes the PREVIOUS lineStart (the reference's order of assignments), inc = (end - start) / (ms / 1000.0 *
+ * sample_rate), triggered and lineComplete are reset; lastTrigVal and trigEnable stay. */
+#define MXG_SHAPE_HARDCLIP 0
+#define MXG_SHAPE_SOFTCLIP 1
+#define MXG_SHAPE_FASTATAN 2
+#define MXG_SHAPE_FASTATANDIST 3
+#define MXG_SHAPE_ATANDIST 4
+#define MXG_SHAPE_ASYMCLIP 5
+#define MXG_SHAPE_MODES 6
+#define MXG_SELECT_MAX_K 64
+#define MXG_XFADE_MAX_C 8
+double mxg_atan_norm_host(double shape);
+int mxg_shape_render(int mode, size_t V, size_t N, const double *d_in, const double *d_a, const double *d_b, int per_sample,
+                     double *d_out, void *stream);
+int mxg_xfade_render(size_t C, size_t V, size_t N, const double *d_ch1, const double *d_ch2, const double *d_xfader,
+                     int xfader_per_sample, double *d_out, void *stream);
+int mxg_select_render(int interpolate, size_t K, size_t V, size_t N, const double *d_index, const double *d_values,
+                      int values_are_signals, int normalised, uint32_t *d_nan_count, double *d_out, void *stream);
+int mxg_line_prepare_host(size_t V, const double *h_start, const double *h_end, const double *h_ms, const int32_t *h_oneshot,
+                          const int32_t *h_mask, double sample_rate, double *h_par, double *h_st);
+int mxg_line_render(size_t V, size_t N, const double *d_trig, double trig_const, const double *d_par, double *d_st, double *d_out,
+                    void *stream);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

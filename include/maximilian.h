@@ -1635,6 +1635,185 @@ private:
     maxiOsc imp;
 };
 
+// ---- maxiNonlinearity / maxiDistortion (H:1046-1139), maxiXFade (H:1491-1527), maxiLine (H:1532-1617), maxiBits
+// (H:1810-1948), maxiSelect / maxiSelectX (H:2018-2088): the small classes that sit between the unit generators, host value
+// types like the analysis classes above.  They restate the reference's arithmetic, expression tree for expression tree, and call
+// std::atan / std::pow: linked against the same libm they give the reference's bits.  Banks of many voices run on the device
+// (maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank in maximilian_bank.hpp, kernel K18; maxiBits has no bank).
+// One defined departure: a NaN index of maxiSelect / maxiSelectX falls through both clamps into a float -> integer cast in the
+// reference (undefined); here it reads element 0.
+class maxiNonlinearity {
+public:
+    maxiNonlinearity() {}
+    double atanDist(const double in, const double shape) { return (1.0 / atan(shape)) * atan(in * shape); }  // H:1125-1130
+    double fastAtanDist(const double in, const double shape) { return (1.0 / fastatan(shape)) * fastatan(in * shape); }  // H:1132-1137
+    double softclip(double x) {  // H:1103-1118
+        if (x >= 1) x = 1;
+        else if (x <= -1) x = -1;
+        else x = (2 / 3.0) * (x - pow(x, 3) / 3.0);
+        return x;
+    }
+    double hardclip(double x) { return x >= 1 ? 1 : (x <= -1 ? -1 : x); }  // H:1098-1102
+    double asymclip(double x, double a, double b) {  // H:1076-1096
+        if (x >= 1) x = 1;
+        else if (x <= -1) x = -1;
+        else if (x < 0) x = -(pow(-x, a));
+        else x = pow(x, b);
+        return x;
+    }
+    double fastatan(double x) { return (x / (1.0 + 0.28 * (x * x))); }  // H:1120-1123
+};
+using maxiDistortion = maxiNonlinearity;  // H:1139
+
+class maxiXFade {
+public:
+    maxiXFade() {}
+    static vector<double> xfade(vector<double> &ch1, vector<double> &ch2, double xfader) {  // H:1502-1514
+        xfader = maxiMap::clamp(xfader, -1, 1);
+        double xfNorm = maxiMap::linlin(xfader, -1, 1, 0, 1);
+        double gainCh1 = sqrt(1.0 - xfNorm);
+        double gainCh2 = sqrt(xfNorm);
+        vector<double> output(ch1.size(), 0.0);
+        for (size_t i = 0; i < output.size(); i++) output[i] = (ch1[i] * gainCh1) + (ch2[i] * gainCh2);
+        return output;
+    }
+    static double xfade(double ch1, double ch2, double xfader) {  // H:1521-1526
+        vector<double> vch1 = {ch1};
+        vector<double> vch2 = {ch2};
+        return maxiXFade::xfade(vch1, vch2, xfader)[0];
+    }
+};
+
+class maxiLine {
+public:
+    maxiLine() {}
+    inline double play(double trigger) {  // H:1537-1568
+        if (!lineComplete) {
+            if (trigEnable && !triggered) {
+                triggered = (trigger > 0.0 && lastTrigVal <= 0.0);
+                lineValue = lineStart;
+            }
+            if (triggered) {
+                lineValue += inc;
+                if (inc <= 0) lineComplete = lineValue <= lineEnd;
+                else lineComplete = lineValue >= lineEnd;
+                if (lineComplete) {
+                    if (!oneShot) reset();
+                }
+            }
+            lastTrigVal = trigger;
+        }
+        return lineValue;
+    }
+    inline void prepare(double start, double end, double durationMs, bool isOneShot) {  // H:1578-1588: lineValue takes the PREVIOUS lineStart
+        lineValue = lineStart;
+        lineStart = start;
+        lineEnd = end;
+        double lineMag = end - start;
+        double durInSamples = durationMs / 1000.0 * maxiSettings::sampleRate;
+        inc = lineMag / durInSamples;
+        oneShot = isOneShot;
+        reset();
+    }
+    inline void triggerEnable(double on) { trigEnable = on > 0.0; }
+    inline bool isLineComplete() { return lineComplete; }
+
+private:
+    double lineValue = 0;
+    double inc = 0;
+    double lastTrigVal = -1;
+    bool trigEnable = false;
+    bool triggered = false;
+    bool lineComplete = false;
+    double lineStart = 0;
+    double lineEnd = 0;
+    bool oneShot = 1;
+    void reset() {
+        triggered = false;
+        lineComplete = false;
+    }
+};
+
+class maxiBits {
+public:
+    typedef uint32_t bitsig;
+    static bitsig sig(bitsig v) { return v; }
+    static bitsig at(const bitsig v, const bitsig idx) { return 1 & (v >> idx); }
+    static bitsig shl(const bitsig v, const bitsig shift) { return v << shift; }
+    static bitsig shr(const bitsig v, const bitsig shift) { return v >> shift; }
+    static bitsig r(const bitsig v, const bitsig offset, const bitsig width) {  // H:1833-1841
+        bitsig mask = maxiBits::l(width);
+        bitsig shift = offset - width + 1;
+        bitsig x = 0;
+        x = v & shl(mask, shift);
+        x = x >> shift;
+        return x;
+    }
+    static bitsig land(const bitsig v, const bitsig x) { return v & x; }
+    static bitsig lor(const bitsig v, const bitsig x) { return v | x; }
+    static bitsig lxor(const bitsig v, const bitsig x) { return v ^ x; }
+    static bitsig neg(const bitsig v) { return ~v; }
+    static bitsig inc(const bitsig v) { return v + 1; }
+    static bitsig dec(const bitsig v) { return v - 1; }
+    static bitsig add(const bitsig v, const bitsig m) { return v + m; }
+    static bitsig sub(const bitsig v, const bitsig m) { return v - m; }
+    static bitsig mul(const bitsig v, const bitsig m) { return v * m; }
+    static bitsig div(const bitsig v, const bitsig m) { return v / m; }
+    static bitsig gt(const bitsig v, const bitsig m) { return v > m; }
+    static bitsig lt(const bitsig v, const bitsig m) { return v < m; }
+    static bitsig gte(const bitsig v, const bitsig m) { return v >= m; }
+    static bitsig lte(const bitsig v, const bitsig m) { return v <= m; }
+    static bitsig eq(const bitsig v, const bitsig m) { return v == m; }
+    static bitsig ct(const bitsig v, const bitsig width) {  // H:1902-1910 (widths up to 31: the reference shifts a signed 1)
+        bitsig x = 0;
+        for (size_t i = 0; i < width; i++) x += (v & ((bitsig)1 << i)) > 0;
+        return x;
+    }
+    static bitsig l(const bitsig width) {  // H:1911-1919
+        bitsig v = 0;
+        for (size_t i = 0; i < width; i++) v += ((bitsig)1 << i);
+        return v;
+    }
+    static bitsig noise() { return static_cast<bitsig>(rand()); }
+    static double toSignal(const bitsig t) { return maxiMap::linlin(t, 0, (double)std::numeric_limits<uint32_t>::max(), -1, 1); }
+    static double toTrigSignal(const bitsig t) { return t > 0 ? 1.0 : -1.0; }
+    static bitsig fromSignal(const double t) {  // H:1937-1942
+        const bitsig halfRange = (std::numeric_limits<uint32_t>::max() / 2);
+        const bitsig val = halfRange + (t * (halfRange - 1));
+        return val;
+    }
+};
+
+class maxiSelect {
+public:
+    maxiSelect() {}
+    double play(double index, vector<double> &values, bool normalised) {  // H:2028-2043
+        auto arrayLen = values.size();
+        if (normalised) index *= (arrayLen - 1e-9);
+        if (index < 0) index = 0;
+        else if (index >= arrayLen) index = arrayLen - 1;
+        if (index != index) index = 0;  // (a NaN index: undefined in the reference)
+        return values[static_cast<size_t>(index)];
+    }
+};
+
+class maxiSelectX {
+public:
+    maxiSelectX() {}
+    double play(double index, vector<double> &values, bool normalised) {  // H:2063-2085
+        auto arrayLen = values.size();
+        if (normalised) index *= (arrayLen - 1e-9);
+        if (index < 0) index = 0;
+        else if (index >= arrayLen) index = arrayLen - 1;
+        if (index != index) index = 0;  // (a NaN index: undefined in the reference)
+        size_t a1 = floor(index);
+        double mix = index - a1;
+        size_t a2 = a1 + 1;
+        if (a2 == arrayLen) a2 = 0;
+        return (values[a1] * (1.0 - mix)) + (values[a2] * mix);
+    }
+};
+
 // ---- maxiKuramotoOscillator (H:1628-1663), maxiKuramotoOscillatorSet (H:1668-1732), maxiAsyncKuramotoOscillator
 // (H:1740-1808): phase-coupled oscillators, host value types like the analysis classes above.  One set is N * N sines per sample
 // and is called between the unit generators, so the classes restate the reference's arithmetic with std::sin: linked against the

@@ -897,6 +897,193 @@ private:
     maxigpu::DeviceArray<int32_t> update_;
 };
 
+// ---- shapers, cross-fade, select and line (H:1046-1139, 1491-1617, 2018-2088; kernel K18) ----------------------------
+// The small classes that sit BETWEEN the other banks: every block is [N][V] on the device, so a chain such as oscillator ->
+// distortion -> filter, or "cross-fade two banks by a line", never leaves it.  The first three are stateless.
+// V x maxiNonlinearity / maxiDistortion (mxg_shape_render): one method per reference call.  The scalar / vector overloads take
+// per-voice parameters; the pointer overloads a device block [N][V] (a parameter per sample).  d_out may be d_in.
+class maxiShaperBank {
+public:
+    explicit maxiShaperBank(size_t voices) : V(voices) {}
+    size_t voices() const { return V; }
+    void hardclip(size_t N, const double *d_in, double *d_out, void *stream = nullptr) { run(MXG_SHAPE_HARDCLIP, N, d_in, nullptr, nullptr, 0, d_out, stream); }
+    void softclip(size_t N, const double *d_in, double *d_out, void *stream = nullptr) { run(MXG_SHAPE_SOFTCLIP, N, d_in, nullptr, nullptr, 0, d_out, stream); }
+    void fastatan(size_t N, const double *d_in, double *d_out, void *stream = nullptr) { run(MXG_SHAPE_FASTATAN, N, d_in, nullptr, nullptr, 0, d_out, stream); }
+    void fastAtanDist(size_t N, const double *d_in, const std::vector<double> &shape, double *d_out, void *stream = nullptr) {
+        per_voice(shape, a_, "fastAtanDist");
+        run(MXG_SHAPE_FASTATANDIST, N, d_in, a_.get(), nullptr, 0, d_out, stream);
+    }
+    void fastAtanDist(size_t N, const double *d_in, double shape, double *d_out, void *stream = nullptr) {
+        fastAtanDist(N, d_in, std::vector<double>(V, shape), d_out, stream);
+    }
+    void fastAtanDist(size_t N, const double *d_in, const double *d_shape, double *d_out, void *stream = nullptr) {
+        run(MXG_SHAPE_FASTATANDIST, N, d_in, d_shape, nullptr, 1, d_out, stream);
+    }
+    void atanDist(size_t N, const double *d_in, const std::vector<double> &shape, double *d_out, void *stream = nullptr) {
+        per_voice(shape, a_, "atanDist");
+        std::vector<double> norm(V);
+        for (size_t v = 0; v < V; v++) norm[v] = mxg_atan_norm_host(shape[v]);  // 1.0 / atan(shape), host libm
+        b_.upload(norm);
+        run(MXG_SHAPE_ATANDIST, N, d_in, a_.get(), b_.get(), 0, d_out, stream);
+    }
+    void atanDist(size_t N, const double *d_in, double shape, double *d_out, void *stream = nullptr) {
+        atanDist(N, d_in, std::vector<double>(V, shape), d_out, stream);
+    }
+    void atanDist(size_t N, const double *d_in, const double *d_shape, double *d_out, void *stream = nullptr) {
+        run(MXG_SHAPE_ATANDIST, N, d_in, d_shape, nullptr, 1, d_out, stream);
+    }
+    void asymclip(size_t N, const double *d_in, const std::vector<double> &a, const std::vector<double> &b, double *d_out, void *stream = nullptr) {
+        per_voice(a, a_, "asymclip");
+        per_voice(b, b_, "asymclip");
+        run(MXG_SHAPE_ASYMCLIP, N, d_in, a_.get(), b_.get(), 0, d_out, stream);
+    }
+    void asymclip(size_t N, const double *d_in, double a, double b, double *d_out, void *stream = nullptr) {
+        asymclip(N, d_in, std::vector<double>(V, a), std::vector<double>(V, b), d_out, stream);
+    }
+    void asymclip(size_t N, const double *d_in, const double *d_a, const double *d_b, double *d_out, void *stream = nullptr) {
+        run(MXG_SHAPE_ASYMCLIP, N, d_in, d_a, d_b, 1, d_out, stream);
+    }
+
+private:
+    void per_voice(const std::vector<double> &p, maxigpu::DeviceArray<double> &d, const char *what) {
+        if (p.size() != V) throw std::runtime_error(std::string("maxiShaperBank::") + what + ": one value per voice");
+        maxigpu::check(mxg_sync(), "mxg_sync");  // (an earlier render may still read the last values)
+        d.upload(p);
+    }
+    void run(int mode, size_t N, const double *d_in, const double *a, const double *b, int ps, double *d_out, void *stream) {
+        maxigpu::check(mxg_shape_render(mode, V, N, d_in, a, b, ps, d_out, stream), "mxg_shape_render");
+    }
+    size_t V;
+    maxigpu::DeviceArray<double> a_, b_;
+};
+
+// V x maxiXFade::xfade over C channels (mxg_xfade_render): d_ch1, d_ch2, d_out are [C][N][V]; the xfader is one value per
+// voice, or a device block [N][V].  d_out may be d_ch1 or d_ch2.
+class maxiXFadeBank {
+public:
+    explicit maxiXFadeBank(size_t voices, size_t channels = 1) : V(voices), C(channels) {
+        if (C < 1 || C > MXG_XFADE_MAX_C) throw std::runtime_error("maxiXFadeBank: 1 .. 8 channels");
+    }
+    size_t voices() const { return V; }
+    size_t channels() const { return C; }
+    void xfade(size_t N, const double *d_ch1, const double *d_ch2, const std::vector<double> &xfader, double *d_out, void *stream = nullptr) {
+        if (xfader.size() != V) throw std::runtime_error("maxiXFadeBank::xfade: one xfader per voice");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        xf_.upload(xfader);
+        maxigpu::check(mxg_xfade_render(C, V, N, d_ch1, d_ch2, xf_.get(), 0, d_out, stream), "mxg_xfade_render");
+    }
+    void xfade(size_t N, const double *d_ch1, const double *d_ch2, double xfader, double *d_out, void *stream = nullptr) {
+        xfade(N, d_ch1, d_ch2, std::vector<double>(V, xfader), d_out, stream);
+    }
+    void xfade(size_t N, const double *d_ch1, const double *d_ch2, const double *d_xfader, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_xfade_render(C, V, N, d_ch1, d_ch2, d_xfader, 1, d_out, stream), "mxg_xfade_render");
+    }
+
+private:
+    size_t V, C;
+    maxigpu::DeviceArray<double> xf_;
+};
+
+// V x maxiSelect (interpolate = false) / maxiSelectX (true) over K = 1 .. 64 values (mxg_select_render).  setValues: K
+// constants for every voice, or K and [K][V]; playSignals reads K device blocks [K][N][V] instead.  A NaN index (undefined in the
+// reference) reads element 0 and is counted per voice in nanCount().
+class maxiSelectBank {
+public:
+    explicit maxiSelectBank(size_t voices, bool interpolate = false) : V(voices), X(interpolate), K(0) { nan_.resize(V); }
+    size_t voices() const { return V; }
+    void setValues(const std::vector<double> &values) {  // K constants shared by the voices
+        std::vector<double> kv(values.size() * V);
+        for (size_t k = 0; k < values.size(); k++)
+            for (size_t v = 0; v < V; v++) kv[k * V + v] = values[k];
+        setValues(values.size(), kv);
+    }
+    void setValues(size_t values, const std::vector<double> &kv) {  // [K][V]
+        if (values < 1 || values > MXG_SELECT_MAX_K || kv.size() != values * V) throw std::runtime_error("maxiSelectBank::setValues: 1 .. 64 values, [K][V]");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        K = values;
+        values_.upload(kv);
+    }
+    void play(size_t N, const double *d_index, bool normalised, double *d_out, void *stream = nullptr) {
+        if (!K) throw std::runtime_error("maxiSelectBank::play: setValues first");
+        maxigpu::check(mxg_select_render(X ? 1 : 0, K, V, N, d_index, values_.get(), 0, normalised ? 1 : 0, nan_.get(), d_out, stream), "mxg_select_render");
+    }
+    void playSignals(size_t N, const double *d_index, size_t values, const double *d_values, bool normalised, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_select_render(X ? 1 : 0, values, V, N, d_index, d_values, 1, normalised ? 1 : 0, nan_.get(), d_out, stream), "mxg_select_render");
+    }
+    std::vector<uint32_t> nanCount() const {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        return nan_.download();
+    }
+
+private:
+    size_t V;
+    bool X;
+    size_t K;
+    maxigpu::DeviceArray<double> values_;
+    maxigpu::DeviceArray<uint32_t> nan_;
+};
+
+// V x maxiLine (mxg_line_render).  prepare / triggerEnable act between two blocks, as the reference's do between two samples;
+// prepare keeps the reference's quirk (lineValue takes the PREVIOUS lineStart).  play(N, d_trig, ...) reads a trigger block
+// [N][V]; play(N, trigger, ...) is the line.play(1) idiom.
+class maxiLineBank {
+public:
+    explicit maxiLineBank(size_t voices) : V(voices) { reset(); }
+    size_t voices() const { return V; }
+    void reset() {  // fresh objects: lineValue 0, lastTrigVal -1, inc 0, one-shot, triggers disabled
+        par_.assign(5 * V, 0.0);
+        st_.assign(4 * V, 0.0);
+        for (size_t v = 0; v < V; v++) { par_[3 * V + v] = 1.0; st_[V + v] = -1.0; }
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_par_.upload(par_);
+        d_st_.upload(st_);
+    }
+    void prepare(const std::vector<double> &start, const std::vector<double> &end, const std::vector<double> &durationMs,
+                 const std::vector<int32_t> &isOneShot, const std::vector<int32_t> *mask = nullptr) {
+        if (start.size() != V || end.size() != V || durationMs.size() != V || isOneShot.size() != V || (mask && mask->size() != V))
+            throw std::runtime_error("maxiLineBank::prepare: one value per voice");
+        pull();
+        maxigpu::check(mxg_line_prepare_host(V, start.data(), end.data(), durationMs.data(), isOneShot.data(), mask ? mask->data() : nullptr,
+                                             (double)maxiSettings::sampleRate, par_.data(), st_.data()), "mxg_line_prepare_host");
+        d_par_.upload(par_);
+        d_st_.upload(st_);
+    }
+    void prepare(double start, double end, double durationMs, bool isOneShot) {
+        prepare(std::vector<double>(V, start), std::vector<double>(V, end), std::vector<double>(V, durationMs), std::vector<int32_t>(V, isOneShot ? 1 : 0));
+    }
+    void triggerEnable(const std::vector<double> &on) {
+        if (on.size() != V) throw std::runtime_error("maxiLineBank::triggerEnable: one value per voice");
+        pull();
+        for (size_t v = 0; v < V; v++) par_[4 * V + v] = on[v] > 0.0 ? 1.0 : 0.0;
+        d_par_.upload(par_);
+    }
+    void triggerEnable(double on) { triggerEnable(std::vector<double>(V, on)); }
+    std::vector<bool> isLineComplete() {
+        pull();
+        std::vector<bool> done(V);
+        for (size_t v = 0; v < V; v++) done[v] = st_[3 * V + v] != 0.0;
+        return done;
+    }
+    void play(size_t N, const double *d_trig, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_line_render(V, N, d_trig, 0.0, d_par_.get(), d_st_.get(), d_out, stream), "mxg_line_render");
+    }
+    void play(size_t N, double trigger, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_line_render(V, N, nullptr, trigger, d_par_.get(), d_st_.get(), d_out, stream), "mxg_line_render");
+    }
+    // parameter and state arrays on the device (include/maxigpu.h): [5][V] and [4][V]
+    double *parameters() { return d_par_.get(); }
+    double *state() { return d_st_.get(); }
+
+private:
+    void pull() {  // the state as the last render left it
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        st_ = d_st_.download();
+    }
+    size_t V;
+    std::vector<double> par_, st_;
+    maxigpu::DeviceArray<double> d_par_, d_st_;
+};
+
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
 namespace maxigpu {
 // lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device

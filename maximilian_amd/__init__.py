@@ -12,6 +12,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiRMSBank, maxiSatReverbBank, maxiFreeVerbBank, maxiFreeVerbStereoBank, reverb_layout, maxiDattaroReverbBank,
                     dattaro_layout, maxiSeqBank, maxiTriggerBank, maxiCounterBank, maxiStepBank, maxiIndexBank,
                     maxiZXToPulseBank, seq_table, seq_ratio_tables, maxiAnalysisBank, maxiKuramotoBank, envfollow_coeff, analysis_want, OSC_WAVEFORMS,
+                    maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, frames_in_stream, padded_stream  # noqa: F401
 from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, WINDOWS  # noqa: F401

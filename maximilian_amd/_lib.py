@@ -122,6 +122,12 @@ SIGNATURES = {
                             [c_int] + [c_void_p] * 7),
     "mxg_kuramoto_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                             c_int, c_void_p, c_void_p, c_void_p]),
+    "mxg_atan_norm_host": (c_double, [c_double]),
+    "mxg_shape_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mxg_xfade_render": (c_int, [c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mxg_select_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mxg_line_prepare_host": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    "mxg_line_render": (c_int, [c_size_t, c_size_t, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

@@ -1218,6 +1218,169 @@ class maxiAnalysisBank(_Bank):
         return res
 
 
+SHAPE_MODES = {"hardclip": 0, "softclip": 1, "fastatan": 2, "fastAtanDist": 3, "atanDist": 4, "asymclip": 5}
+SELECT_MAX_K = 64
+XFADE_MAX_C = 8
+
+
+def atan_norm(shape):
+    """1.0 / atan(shape) with the host libm (mxg_atan_norm_host): atanDist's factor, the reference's own expression (H:1128)."""
+    f = lib().mxg_atan_norm_host
+    return np.array([f(float(s)) for s in np.atleast_1d(np.asarray(shape, np.float64)).reshape(-1)]).reshape(np.shape(shape))
+
+
+class maxiShaperBank(_Bank):
+    """V x maxiNonlinearity / maxiDistortion over one block [N][V] (H:1046-1139; mxg_shape_render, K18).  One method per
+    reference call; parameters are scalar / [V], or a device or host [N][V] block (one value per sample).  out may be x (in
+    place).  hardclip, fastatan and fastAtanDist are the reference's bits; softclip is within 2^-52 of it; atanDist and asymclip
+    use the device's atan / pow (tolerance)."""
+
+    def _render(self, mode, x, a=None, b=None, out=None):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        pa = pb = None
+        ps = 0
+        if a is not None:
+            pa, ps = _fx_param(a, self.V, N, np.float64, "shape" if b is None else "a")
+        if mode == "asymclip":
+            pb, psb = _fx_param(b, self.V, N, np.float64, "b")
+            if psb != ps:   # one flag for both: the per-voice one is spread over the block
+                if ps:
+                    pb = DeviceBuffer.from_numpy(np.broadcast_to(pb.numpy(), (N, self.V)))
+                else:
+                    pa, ps = DeviceBuffer.from_numpy(np.broadcast_to(pa.numpy(), (N, self.V))), 1
+        elif mode == "atanDist" and not ps:
+            pb = DeviceBuffer.from_numpy(atan_norm(pa.numpy() if isinstance(pa, DeviceBuffer) else pa.cpu().numpy()))
+        out = self._out(N, out)
+        check(lib().mxg_shape_render(SHAPE_MODES[mode], self.V, N, _ptr(x), _ptr(pa), _ptr(pb), ps, _ptr(out), self.stream),
+              "mxg_shape_render")
+        return out
+
+    def hardclip(self, x, out=None):
+        return self._render("hardclip", x, out=out)
+
+    def softclip(self, x, out=None):
+        return self._render("softclip", x, out=out)
+
+    def fastatan(self, x, out=None):
+        return self._render("fastatan", x, out=out)
+
+    def fastAtanDist(self, x, shape, out=None):
+        return self._render("fastAtanDist", x, shape, out=out)
+
+    def atanDist(self, x, shape, out=None):
+        return self._render("atanDist", x, shape, out=out)
+
+    def asymclip(self, x, a, b, out=None):
+        return self._render("asymclip", x, a, b, out=out)
+
+
+class maxiXFadeBank(_Bank):
+    """V x maxiXFade::xfade over C = 1 .. 8 channels (H:1491-1527; mxg_xfade_render, K18): ch1, ch2 are device [C][N][V] (or
+    [N][V] for C = 1), xfader scalar / [V] or a device or host [N][V] block.  Bit-exact."""
+
+    def xfade(self, ch1, ch2, xfader, out=None):
+        shape = tuple(ch1.shape)
+        C, N = (1, shape[0]) if len(shape) == 2 else (shape[0], shape[1])
+        if not 1 <= C <= XFADE_MAX_C:
+            raise ValueError("C: 1 .. %d channels, got %d" % (XFADE_MAX_C, C))
+        for c, what in ((ch1, "ch1"), (ch2, "ch2")):
+            _fx_dev(c, np.float64, what, (C * N * self.V,))
+        xf, ps = _fx_param(xfader, self.V, N, np.float64, "xfader")
+        if out is None:
+            out = DeviceBuffer(shape, np.float64, zero=False)
+        check(lib().mxg_xfade_render(C, self.V, N, _ptr(ch1), _ptr(ch2), _ptr(xf), ps, _ptr(out), self.stream), "mxg_xfade_render")
+        return out
+
+
+class maxiSelectBank(_Bank):
+    """V x maxiSelect (interpolate=False) / maxiSelectX (True) over K = 1 .. 64 values (H:2018-2088; mxg_select_render, K18).
+    values: host [K] / [K][V] constants (kept on the device), or a device [K][N][V] block of signals.  A NaN index is undefined
+    in the reference; here it reads element 0 and is counted per voice in `nan_count`.  Bit-exact."""
+
+    def __init__(self, voices, interpolate=False, stream=None):
+        super().__init__(voices, stream)
+        self.interpolate = bool(interpolate)
+        self.nan_count = DeviceBuffer(self.V, np.uint32)
+
+    def play(self, index, values, normalised=False, out=None):
+        N = index.shape[0]
+        _fx_dev(index, np.float64, "index", (N * self.V,))
+        if isinstance(values, DeviceBuffer) or hasattr(values, "data_ptr"):
+            K = int(values.shape[0])
+            n = _fx_dev(values, np.float64, "values", (K * self.V, K * N * self.V))
+            sig = int(n == K * N * self.V and (N > 1 or len(values.shape) == 3))
+        else:
+            a = np.asarray(values, np.float64)
+            K = a.shape[0]
+            values = DeviceBuffer.from_numpy(np.broadcast_to(a.reshape(K, -1), (K, self.V)))
+            sig = 0
+        if not 1 <= K <= SELECT_MAX_K:
+            raise ValueError("K: 1 .. %d values, got %d" % (SELECT_MAX_K, K))
+        out = self._out(N, out)
+        check(lib().mxg_select_render(int(self.interpolate), K, self.V, N, _ptr(index), _ptr(values), sig, int(bool(normalised)),
+                                      self.nan_count.ptr, _ptr(out), self.stream), "mxg_select_render")
+        return out
+
+
+class maxiLineBank(_Bank):
+    """V x maxiLine (H:1532-1617; mxg_line_render, K18).  par [5][V] = lineStart, lineEnd, inc, oneShot, trigEnable; state
+    [4][V] = lineValue, lastTrigVal, triggered, lineComplete.  prepare() keeps the reference's quirk: lineValue takes the
+    previous lineStart.  Bit-exact, the state included."""
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        self.par = DeviceBuffer((5, self.V))
+        self.reset()
+
+    def reset(self):
+        """Fresh objects: lineValue 0, lastTrigVal -1, inc 0, one-shot, triggers disabled."""
+        par = np.zeros((5, self.V))
+        par[3] = 1.0
+        self.par.upload(par)
+        st = np.zeros((4, self.V))
+        st[1] = -1.0
+        self.state = DeviceBuffer.from_numpy(st)
+
+    def prepare(self, start, end, durationMs, isOneShot, voices=None):
+        """maxiLine::prepare on every voice, or on `voices` (indices); arguments scalar or [V]."""
+        V = self.V
+        par, st = self.par.numpy(), self.state.numpy()
+        s, e, ms = (np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (V,))) for a in (start, end, durationMs))
+        one = np.ascontiguousarray(np.broadcast_to(np.asarray(isOneShot), (V,)).astype(np.int32))
+        mask = None
+        if voices is not None:
+            mask = np.zeros(V, np.int32)
+            mask[np.atleast_1d(np.asarray(voices, np.int64))] = 1
+        check(lib().mxg_line_prepare_host(V, s.ctypes.data, e.ctypes.data, ms.ctypes.data, one.ctypes.data,
+                                          None if mask is None else mask.ctypes.data, float(maxiSettings.sampleRate),
+                                          par.ctypes.data, st.ctypes.data), "mxg_line_prepare_host")
+        self.par.upload(par)
+        self.state.upload(st)
+
+    def triggerEnable(self, on):
+        par = self.par.numpy()
+        par[4] = (np.broadcast_to(np.asarray(on, np.float64), (self.V,)) > 0.0).astype(np.float64)
+        self.par.upload(par)
+
+    def isLineComplete(self):
+        return self.state.numpy()[3] != 0.0
+
+    def play(self, trigger, N=None, out=None):
+        """trigger: a device [N][V] block, or a number played on N samples (line.play(1))."""
+        if isinstance(trigger, DeviceBuffer) or hasattr(trigger, "data_ptr"):
+            N = trigger.shape[0]
+            _fx_dev(trigger, np.float64, "trigger", (N * self.V,))
+            tp, tc = _ptr(trigger), 0.0
+        else:
+            if N is None:
+                raise ValueError("N: a constant trigger needs the number of samples")
+            tp, tc = None, float(trigger)
+        out = self._out(int(N), out)
+        check(lib().mxg_line_render(self.V, int(N), tp, tc, self.par.ptr, self.state.ptr, _ptr(out), self.stream), "mxg_line_render")
+        return out
+
+
 KURAMOTO_WANT = {"mix": 1, "phases": 2}
 KURAMOTO_MAX_N = 64
 
