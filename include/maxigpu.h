@@ -942,6 +942,40 @@ int mxg_mfcc_plan_matrix_tables(const mxg_mfcc_plan *plan, int *h_nb, int *h_bas
 int mxg_mfcc_batch(const mxg_mfcc_plan *plan, const float *d_mags, size_t mag_stride, size_t nframes,
                    double *d_melraw, double *d_melbands, double *d_mfcc, int method, void *stream);
 
+/* ---- maxiBark / maxiFFTOctaveAnalyzer batches (K19, bands.hip) ------------------------------------------------------- */
+/* maxiBarkScaleAnalyser<double>::setup(sR, bS) (L/maxiBark.h:40-62): the 25 band limits, built on the host libm (works without a
+ * device).  Limit 24 is specSize - 1 = bufferSize / 2 - 1, as the reference reads it back: the last bin is never summed, bands can
+ * be empty.  NULL + MXG_ERR_INVALID: bufferSize outside [2, 4096] (the reference's barkScale[2048]), a bin * sampleRate that
+ * overflows 32 bits. */
+#define MXG_BARK_BANDS 24
+typedef struct mxg_bark_plan mxg_bark_plan;
+mxg_bark_plan *mxg_bark_plan_create(unsigned sampleRate, unsigned bufferSize);
+int mxg_bark_plan_destroy(mxg_bark_plan *plan);
+int mxg_bark_plan_limits(const mxg_bark_plan *plan, int *h_limits /* [25] */);
+/* specificLoudness / relativeLoudness / totalLoudness (L/maxiBark.h:64-116) over nframes rows d_spectrum[f*stride + bin] (fp32,
+ * stride >= bufferSize / 2) -> d_bandsum / d_specific / d_relative [nframes][24], d_total [nframes].  Any output may be NULL: a
+ * stage not asked for neither runs nor touches its array.  The band sums are bit-exact (a double accumulated bin after bin);
+ * specific = pow(sum, 0.23) is the device library's pow (tolerance: DESIGN.md, K19).  A silent frame gives 24 NaNs in d_relative. */
+int mxg_bark_batch(const mxg_bark_plan *plan, const float *d_spectrum, size_t stride, size_t nframes, double *d_bandsum,
+                   double *d_specific, double *d_relative, double *d_total, void *stream);
+/* maxiFFTOctaveAnalyzer::setup (L/maxiFFT.cpp:207-259): the spe2avg map in float arithmetic, on the host (works without a device).
+ * NULL + MXG_ERR_INVALID: nSpectrum outside [1, 4096], a non-finite or non-positive samplingRate, a negative nAveragesPerOctave
+ * (the reference's setup() does not return), more than 16384 averages, and -- a defined departure -- a configuration with
+ * nAverages == 0 (samplingRate / 2 at or below the first band's 55 Hz), which the reference sets up as an analyser of nothing. */
+typedef struct mxg_octave_plan mxg_octave_plan;
+mxg_octave_plan *mxg_octave_plan_create(float samplingRate, int nSpectrum, int nAveragesPerOctave);
+int mxg_octave_plan_destroy(mxg_octave_plan *plan);
+int mxg_octave_plan_averages(const mxg_octave_plan *plan);              /* nAverages */
+int mxg_octave_plan_map(const mxg_octave_plan *plan, int *h_spe2avg);   /* [nSpectrum] */
+/* calculate() (L/maxiFFT.cpp:261-300) for nstreams analysers over frames_per_stream frames each: frame g = s*frames_per_stream + k
+ * is row d_mags[g*stride + bin] (stride >= nSpectrum).  d_averages and the optional d_peaks_out are
+ * [nstreams*frames_per_stream][nAverages].  d_peak_state / d_hold_state [nstreams][nAverages] are peaks / peakHoldTimes, in and
+ * out, carried from call to call (a fresh analyser: zeros); both NULL = no peak pass.  All float, bit-exact.  One stream's frames
+ * are walked in order by one thread per average: the peak pass is serial in time. */
+int mxg_octave_batch(const mxg_octave_plan *plan, const float *d_mags, size_t stride, size_t nstreams, size_t frames_per_stream,
+                     float eq_intercept, float eq_slope, int peakHoldTime, float peakDecayRate, float *d_averages, float *d_peaks_out,
+                     float *d_peak_state, int32_t *d_hold_state, void *stream);
+
 /* ---- maxiFFT + maxiMFCC in one pass (the loop of cpp/commandline/tests/mfcctest/mfcctest.cpp:21-32 over a batch) ---- */
 /* For every frame k = d_signal[k*frame_stride .. +1024): mags = maxiFFT(1024).process(...) magnitudes (L/fft.cpp:499-511),
  * then maxiMFCC::mfcc(mags) (L/maxiMFCC.h:77-81) -> d_mfcc [nframes][numCoeffs], in ONE kernel: the magnitudes stay in

@@ -3172,6 +3172,130 @@ private:
     std::vector<float> hop_;
 };
 
+// ---- maxiFFTOctaveAnalyzer (L/maxiFFT.h:162-205; L/maxiFFT.cpp:207-300): one frame per calculate() on the device (K19) -----------
+// The reference's public members are kept, and the public arrays ARE the state: calculate() uploads peaks / peakHoldTimes, runs
+// one frame and downloads averages, peaks and peakHoldTimes, so a patch that reads or writes them between calls sees what it would
+// in the reference.  A fresh object starts the three arrays at 0 (the reference leaves them uninitialised).  All float, bit-exact.
+class maxiFFTOctaveAnalyzer {
+public:
+    float samplingRate = 0;
+    int nSpectrum = 0;
+    int nAverages = 0;
+    int nAveragesPerOctave = 0;
+    float spectrumFrequencySpan = 0;
+    float firstOctaveFrequency = 0;
+    float averageFrequencyIncrement = 0;
+    float *averages = nullptr;
+    float *peaks = nullptr;
+    int *peakHoldTimes = nullptr;
+    int peakHoldTime = 0;
+    float peakDecayRate = 0;
+    int *spe2avg = nullptr;
+    float linearEQSlope = 0;
+    float linearEQIntercept = 0;
+
+    maxiFFTOctaveAnalyzer() {}
+    ~maxiFFTOctaveAnalyzer() { release(); }
+    maxiFFTOctaveAnalyzer(const maxiFFTOctaveAnalyzer &o) { copy_from(o); }
+    maxiFFTOctaveAnalyzer &operator=(const maxiFFTOctaveAnalyzer &o) { if (this != &o) copy_from(o); return *this; }
+
+    void setup(float samplingRate_, int nBandsInTheFFT, int nAveragesPerOctave_) {  // L/maxiFFT.cpp:207-259
+        MAXIGPU_TRY {
+        release();
+        plan_ = mxg_octave_plan_create(samplingRate_, nBandsInTheFFT, nAveragesPerOctave_);
+        if (!plan_) maxigpu::ps::fatal(std::string("mxg_octave_plan_create: ") + mxg_last_error());
+        samplingRate = samplingRate_;
+        nSpectrum = nBandsInTheFFT;
+        askedPerOctave_ = nAveragesPerOctave_;
+        nAveragesPerOctave = nAveragesPerOctave_ == 0 ? 1 : nAveragesPerOctave_;
+        spectrumFrequencySpan = (samplingRate_ / 2.0f) / (float)(nSpectrum);
+        averageFrequencyIncrement = powf(2.0f, 1.0f / (float)(nAveragesPerOctave));
+        firstOctaveFrequency = 55.0f;
+        nAverages = mxg_octave_plan_averages(plan_);
+        map_.assign((size_t)nSpectrum, 0);
+        mxg_octave_plan_map(plan_, map_.data());
+        avg_.assign((size_t)nAverages, 0.0f);
+        pk_.assign((size_t)nAverages, 0.0f);
+        hold_.assign((size_t)nAverages, 0);
+        point();
+        peakHoldTime = 0;
+        peakDecayRate = 0.9f;
+        linearEQIntercept = 1.0f;
+        linearEQSlope = 0.0f;
+        d_in_ = static_cast<float *>(mxg_malloc(sizeof(float) * (size_t)nSpectrum));
+        d_f_ = static_cast<float *>(mxg_malloc(sizeof(float) * 2 * (size_t)nAverages));
+        d_h_ = static_cast<int32_t *>(mxg_malloc(sizeof(int32_t) * (size_t)nAverages));
+        if (!d_in_ || !d_f_ || !d_h_) maxigpu::ps::fatal(std::string("mxg_malloc: ") + mxg_last_error());
+        }
+        MAXIGPU_CATCH(return)
+    }
+    void calculate(float *fftData) {  // :261-300
+        using maxigpu::ps::check;
+        if (!plan_) {
+            maxigpu::ps::complain("maxiFFTOctaveAnalyzer::calculate before setup()");
+            return;
+        }
+        if (maxigpu::ps::dead()) {
+            std::fill(avg_.begin(), avg_.end(), 0.0f);
+            return;
+        }
+        const size_t nA = (size_t)nAverages;
+        check(mxg_memcpy_h2d(d_in_, fftData, sizeof(float) * (size_t)nSpectrum, nullptr), "h2d spectrum");
+        check(mxg_memcpy_h2d(d_f_ + nA, peaks, sizeof(float) * nA, nullptr), "h2d peaks");
+        check(mxg_memcpy_h2d(d_h_, peakHoldTimes, sizeof(int32_t) * nA, nullptr), "h2d peakHoldTimes");
+        check(mxg_octave_batch(plan_, d_in_, (size_t)nSpectrum, 1, 1, linearEQIntercept, linearEQSlope, peakHoldTime, peakDecayRate, d_f_, nullptr,
+                               d_f_ + nA, d_h_, nullptr), "mxg_octave_batch");
+        check(mxg_memcpy_d2h(averages, d_f_, sizeof(float) * nA, nullptr), "d2h averages");
+        check(mxg_memcpy_d2h(peaks, d_f_ + nA, sizeof(float) * nA, nullptr), "d2h peaks");
+        check(mxg_memcpy_d2h(peakHoldTimes, d_h_, sizeof(int32_t) * nA, nullptr), "d2h peakHoldTimes");
+    }
+
+private:
+    void point() {
+        averages = avg_.data();
+        peaks = pk_.data();
+        peakHoldTimes = hold_.data();
+        spe2avg = map_.data();
+    }
+    void release() {
+        if (plan_) mxg_octave_plan_destroy(plan_);
+        if (d_in_) mxg_free(d_in_);
+        if (d_f_) mxg_free(d_f_);
+        if (d_h_) mxg_free(d_h_);
+        plan_ = nullptr;
+        d_in_ = d_f_ = nullptr;
+        d_h_ = nullptr;
+    }
+    void copy_from(const maxiFFTOctaveAnalyzer &o) {  // the public arrays are the state: copied, parameters too
+        if (!o.plan_) {  // a copy of an analyser that was never set up is one
+            release();
+            samplingRate = spectrumFrequencySpan = firstOctaveFrequency = averageFrequencyIncrement = 0;
+            nSpectrum = nAverages = nAveragesPerOctave = askedPerOctave_ = 0;
+            peakHoldTime = 0;
+            peakDecayRate = linearEQSlope = linearEQIntercept = 0;
+            avg_.clear(); pk_.clear(); hold_.clear(); map_.clear();
+            averages = peaks = nullptr;
+            peakHoldTimes = spe2avg = nullptr;
+            return;
+        }
+        setup(o.samplingRate, o.nSpectrum, o.askedPerOctave_);
+        if ((int)avg_.size() != o.nAverages) return;  // (the device path is dead)
+        std::copy(o.averages, o.averages + o.nAverages, avg_.begin());
+        std::copy(o.peaks, o.peaks + o.nAverages, pk_.begin());
+        std::copy(o.peakHoldTimes, o.peakHoldTimes + o.nAverages, hold_.begin());
+        peakHoldTime = o.peakHoldTime;
+        peakDecayRate = o.peakDecayRate;
+        linearEQSlope = o.linearEQSlope;
+        linearEQIntercept = o.linearEQIntercept;
+    }
+    mxg_octave_plan *plan_ = nullptr;
+    int askedPerOctave_ = 0;
+    float *d_in_ = nullptr, *d_f_ = nullptr;
+    int32_t *d_h_ = nullptr;
+    std::vector<float> avg_, pk_;
+    std::vector<int> hold_, map_;
+};
+
 // ---- the plugin API (src/maximilian.cpp:205-207; cpp/commandline/player.cpp:21-44) ------------------------------------
 void setup();
 void play(double *output);

@@ -1389,6 +1389,62 @@ private:
     unsigned numBins_ = 0;
 };
 
+// ---- maxiBark / maxiFFTOctaveAnalyzer over batches of magnitude rows (K19) ---------------------------------------------------
+class maxiBarkBatch {
+public:
+    ~maxiBarkBatch() { if (plan_) mxg_bark_plan_destroy(plan_); }
+    void setup(unsigned sampleRate, unsigned bufferSize) {  // L/maxiBark.h:40-62
+        if (plan_) mxg_bark_plan_destroy(plan_);
+        plan_ = mxg_bark_plan_create(sampleRate, bufferSize);
+        if (!plan_) throw std::runtime_error(std::string("mxg_bark_plan_create: ") + mxg_last_error());
+        specSize_ = bufferSize / 2;
+    }
+    std::vector<int> limits() const {
+        std::vector<int> lim(MXG_BARK_BANDS + 1);
+        maxigpu::check(mxg_bark_plan_limits(plan_, lim.data()), "mxg_bark_plan_limits");
+        return lim;
+    }
+    // d_spectrum [nframes][bufferSize / 2] -> any of d_specific / d_relative [nframes][24], d_total [nframes], d_bandsum (null: not produced)
+    void analyse(const float *d_spectrum, size_t nframes, double *d_specific, double *d_relative = nullptr, double *d_total = nullptr,
+                 double *d_bandsum = nullptr, void *stream = nullptr) {
+        maxigpu::check(mxg_bark_batch(plan_, d_spectrum, specSize_, nframes, d_bandsum, d_specific, d_relative, d_total, stream), "mxg_bark_batch");
+    }
+
+private:
+    mxg_bark_plan *plan_ = nullptr;
+    unsigned specSize_ = 0;
+};
+
+class maxiOctaveBatch {
+public:
+    int peakHoldTime = 0;            // L/maxiFFT.cpp:255-258
+    float peakDecayRate = 0.9f, linearEQIntercept = 1.0f, linearEQSlope = 0.0f;
+    explicit maxiOctaveBatch(size_t streams = 1) : S(streams) {}
+    ~maxiOctaveBatch() { if (plan_) mxg_octave_plan_destroy(plan_); }
+    void setup(float samplingRate, int nSpectrum, int nAveragesPerOctave) {  // L/maxiFFT.cpp:207-259; peaks and hold counters start at 0
+        if (plan_) mxg_octave_plan_destroy(plan_);
+        plan_ = mxg_octave_plan_create(samplingRate, nSpectrum, nAveragesPerOctave);
+        if (!plan_) throw std::runtime_error(std::string("mxg_octave_plan_create: ") + mxg_last_error());
+        nSpectrum_ = nSpectrum;
+        nAverages_ = mxg_octave_plan_averages(plan_);
+        peaks_ = maxigpu::DeviceArray<float>(S * (size_t)nAverages_);
+        hold_ = maxigpu::DeviceArray<int32_t>(S * (size_t)nAverages_);
+    }
+    int nAverages() const { return nAverages_; }
+    // d_mags [streams * frames][nSpectrum], stream-major -> d_averages and (optional) d_peaks [streams * frames][nAverages]
+    void calculate(const float *d_mags, size_t frames, float *d_averages, float *d_peaks = nullptr, void *stream = nullptr) {
+        maxigpu::check(mxg_octave_batch(plan_, d_mags, (size_t)nSpectrum_, S, frames, linearEQIntercept, linearEQSlope, peakHoldTime, peakDecayRate,
+                                        d_averages, d_peaks, peaks_.get(), hold_.get(), stream), "mxg_octave_batch");
+    }
+    const size_t S;
+
+private:
+    mxg_octave_plan *plan_ = nullptr;
+    int nSpectrum_ = 0, nAverages_ = 0;
+    maxigpu::DeviceArray<float> peaks_;
+    maxigpu::DeviceArray<int32_t> hold_;
+};
+
 // ---- maxiTimeStretch / maxiStretch banks (L/maxiGrains.h) ---------------------------------------------------------
 class maxiTimeStretchBank {
 public:

@@ -14,5 +14,6 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiZXToPulseBank, seq_table, seq_ratio_tables, maxiAnalysisBank, maxiKuramotoBank, envfollow_coeff, analysis_want, OSC_WAVEFORMS,
                     maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
                     FILTER_KINDS, SAMPLE_MODES)
-from .spectral import maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, frames_in_stream, padded_stream  # noqa: F401
+from .spectral import (maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
+                       padded_stream)
 from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, WINDOWS  # noqa: F401

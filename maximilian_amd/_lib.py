@@ -160,6 +160,16 @@ SIGNATURES = {
     "mxg_mfcc_plan_matrix_tables": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mxg_mfcc_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p,
                                c_int, c_void_p]),
+    "mxg_bark_plan_create": (c_void_p, [ctypes.c_uint, ctypes.c_uint]),
+    "mxg_bark_plan_destroy": (c_int, [c_void_p]),
+    "mxg_bark_plan_limits": (c_int, [c_void_p, c_void_p]),
+    "mxg_bark_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_octave_plan_create": (c_void_p, [ctypes.c_float, c_int, c_int]),
+    "mxg_octave_plan_destroy": (c_int, [c_void_p]),
+    "mxg_octave_plan_averages": (c_int, [c_void_p]),
+    "mxg_octave_plan_map": (c_int, [c_void_p, c_void_p]),
+    "mxg_octave_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, ctypes.c_float, ctypes.c_float, c_int,
+                                 ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_fft_mfcc_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
     "mxg_grain_plan_create": (c_void_p, [c_int, c_double, c_int]),

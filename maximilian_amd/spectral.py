@@ -175,6 +175,108 @@ class maxiMFCC:
             pass
 
 
+class maxiBarkBatch:
+    """maxiBarkScaleAnalyser<double> (L/maxiBark.h, alias maxiBark) over batches of spectra: specificLoudness /
+    relativeLoudness / totalLoudness of every row of [nframes, >= bufferSize / 2] fp32 magnitudes (mxg_bark_batch)."""
+    NUM_BARK_BANDS = 24
+
+    def __init__(self, stream=None):
+        self.plan = None
+        self.stream = stream
+
+    def setup(self, sampleRate, bufferSize):
+        """L/maxiBark.h:40-62; the limits are built on the host and need no device."""
+        self.close()
+        p = lib().mxg_bark_plan_create(int(sampleRate), int(bufferSize))
+        if not p:
+            raise ValueError(lib().mxg_last_error().decode())
+        self.plan = p
+        self.sampleRate, self.bufferSize, self.specSize = int(sampleRate), int(bufferSize), int(bufferSize) // 2
+
+    def limits(self):
+        lim = np.zeros(25, np.int32)
+        check(lib().mxg_bark_plan_limits(self.plan, lim.ctypes.data), "mxg_bark_plan_limits")
+        return lim
+
+    def analyse(self, mags, nframes=None, stride=None, bandsum=False, specific=True, relative=False, total=False):
+        """-> dict of the DeviceBuffers asked for: bandsum / specific / relative [nframes, 24], total [nframes]."""
+        nframes = mags.shape[0] if nframes is None else nframes
+        stride = self.specSize if stride is None else stride
+        want = {"bandsum": bandsum, "specific": specific, "relative": relative, "total": total}
+        out = {k: DeviceBuffer(nframes if k == "total" else (nframes, 24), np.float64, zero=False) for k, w in want.items() if w}
+        check(lib().mxg_bark_batch(self.plan, _ptr(mags), stride, nframes, _ptr(out.get("bandsum")), _ptr(out.get("specific")),
+                                   _ptr(out.get("relative")), _ptr(out.get("total")), self.stream), "mxg_bark_batch")
+        return out
+
+    def specificLoudness(self, mags): return self.analyse(mags)["specific"]
+    def relativeLoudness(self, mags): return self.analyse(mags, specific=False, relative=True)["relative"]
+    def totalLoudness(self, mags): return self.analyse(mags, specific=False, total=True)["total"]
+
+    def close(self):
+        if self.plan:
+            lib().mxg_bark_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class maxiOctaveBatch:
+    """maxiFFTOctaveAnalyzer (L/maxiFFT.h:162-205) for `streams` analysers: calculate(mags) takes [streams * frames, >= nSpectrum]
+    fp32 magnitudes (stream-major) and returns the averages and peaks of every frame; peaks / peakHoldTimes are carried."""
+
+    def __init__(self, streams=1, stream=None):
+        self.plan = None
+        self.S = int(streams)
+        self.stream = stream
+        self.peakHoldTime, self.peakDecayRate = 0, 0.9            # L/maxiFFT.cpp:255-258
+        self.linearEQIntercept, self.linearEQSlope = 1.0, 0.0
+
+    def setup(self, samplingRate, nSpectrum, nAveragesPerOctave):
+        """L/maxiFFT.cpp:207-259; a fresh bank's peaks and hold counters are zeros."""
+        self.close()
+        p = lib().mxg_octave_plan_create(float(samplingRate), int(nSpectrum), int(nAveragesPerOctave))
+        if not p:
+            raise ValueError(lib().mxg_last_error().decode())
+        self.plan = p
+        self.nSpectrum = int(nSpectrum)
+        self.nAverages = lib().mxg_octave_plan_averages(p)
+        self.spe2avg = np.zeros(self.nSpectrum, np.int32)
+        check(lib().mxg_octave_plan_map(p, self.spe2avg.ctypes.data), "mxg_octave_plan_map")
+        self.peaks = self.peakHoldTimes = None
+
+    def calculate(self, mags, frames=None, stride=None, peaks=True):
+        """-> (averages, peaks or None), DeviceBuffers [streams * frames, nAverages]."""
+        frames = mags.shape[0] // self.S if frames is None else frames
+        stride = self.nSpectrum if stride is None else stride
+        avg = DeviceBuffer((self.S * frames, self.nAverages), np.float32, zero=False)
+        pk = None
+        if peaks:
+            if self.peaks is None:
+                self.peaks = DeviceBuffer((self.S, self.nAverages), np.float32)
+                self.peakHoldTimes = DeviceBuffer((self.S, self.nAverages), np.int32)
+            pk = DeviceBuffer((self.S * frames, self.nAverages), np.float32, zero=False)
+        check(lib().mxg_octave_batch(self.plan, _ptr(mags), stride, self.S, frames, self.linearEQIntercept, self.linearEQSlope,
+                                     int(self.peakHoldTime), self.peakDecayRate, _ptr(avg), _ptr(pk),
+                                     _ptr(self.peaks) if peaks else None, _ptr(self.peakHoldTimes) if peaks else None, self.stream),
+              "mxg_octave_batch")
+        return avg, pk
+
+    def close(self):
+        if self.plan:
+            lib().mxg_octave_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class maxiIFFT:
     """maxiIFFT (L/maxiFFT.h:117-156, SPECTRUM mode) over batches of spectra: `process_frames(mags, phases)`
     returns the nframes*hopSize samples `process()` would return when called hopSize times per spectrum;
