@@ -14,12 +14,12 @@
 // 64 samples (one word written, one or two read).  HBM per sample and voice: 8 B in + 8 B per requested output (+ 8 B for a
 // per-sample hold time) + 0.25-0.4 B of ring.
 //
-// Shape, as envgen.hip / seq.hip: one lane = one voice, chunks of 8 samples, surplus lanes shadow the last voice (pair) and
+// Shape (mxg_stream.h), as envgen.hip / seq.hip: one lane = one voice, chunks of 8 samples, surplus lanes shadow the last voice (pair) and
 // store no state, whole chunks leave through emit_chunk (8-byte stores or 16-byte pair rows), the input is requested a chunk
 // ahead and consumed before the chunk's stores.  Banks of up to 16 384 voices run in workgroups of one wavefront (dyn.hip), so
 // that they still spread over the compute units.  No scratch.
 #include "mxg_common.h"
-#include "mxg_gate.h"
+#include "mxg_stream.h"
 #include "mxg_analysis.h"
 
 namespace mxg {
@@ -46,28 +46,13 @@ struct AnaArgs {
     int px_store;
 };
 
-// a whole chunk through emit_chunk; the first cnt rows of a ragged last one by 8-byte stores
-template <bool PX, int U>
-__device__ __forceinline__ void ana_emit(double *&op, size_t V, const double (&y)[U], int cnt, int px_store) {
-    if (cnt == U) {
-        emit_chunk<PX>(op, V, y, px_store);
-    } else {
-#pragma unroll
-        for (int i = 0; i < U; i++) {
-            if (i >= cnt) break;
-            *op = y[i];
-            op += V;
-        }
-    }
-}
-
 template <bool PX>
 __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
     const size_t V = A.V, N = A.N;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if ((gid & ~(size_t)63) >= V) return;  // the whole wavefront is past the bank
+    if (bank_wave_idle(gid, V)) return;
     const bool live = gid < V;
-    const size_t v = PX ? (live ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    const size_t v = bank_voice<PX>(gid, V);
     const int want = A.want;
     const bool w_zcr = (want & MXG_ANA_WANT_ZCR) != 0, w_zx = (want & (MXG_ANA_WANT_ZX | MXG_ANA_WANT_ZCR)) != 0;
     const bool w_env = (want & MXG_ANA_WANT_ENV) != 0, w_sah = (want & MXG_ANA_WANT_SAH) != 0;
@@ -98,26 +83,20 @@ __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
     const double *__restrict__ ip = A.in + v;
     const double *__restrict__ hp = hold_ps ? A.hold_ms + v : nullptr;
     double xn[U];
-#pragma unroll
-    for (int i = 0; i < U; i++) {
-        const size_t m = (size_t)i < N ? (size_t)i : N - 1;
-        xn[i] = ip[m * V];
-    }
-    // consume every prologue load here (envgen.hip): a use inside the loop would be a counted wait that drains the output stores
+    rows_first(xn, ip, V, N);
+    // consume every prologue load here (mxg_stream.h)
     asm volatile("" : "+v"(prev), "+v"(att), "+v"(rel), "+v"(env), "+v"(phase), "+v"(held), "+v"(hold), "+v"(z.head), "+v"(z.count));
     double *ozx = (want & MXG_ANA_WANT_ZX) ? A.o_zx + v : nullptr, *ozc = w_zcr ? A.o_zcr + v : nullptr;
     double *oen = w_env ? A.o_env + v : nullptr, *osh = w_sah ? A.o_sah + v : nullptr;
     // one stage after the other over the chunk, each leaving through emit_chunk: one chunk of results is live at a time
     for (size_t n0 = 0; n0 < N; n0 += U) {
         double xc[U], hc[U];
+        rows_next(xc, xn, ip, V, N, n0);
+        if (hold_ps) {
 #pragma unroll
-        for (int i = 0; i < U; i++) {
-            xc[i] = xn[i];
-            const size_t m = (n0 + U + i < N) ? n0 + U + i : N - 1;  // clamped prefetch, a chunk ahead of the stores
-            xn[i] = ip[m * V];
-            if (hold_ps) hc[i] = hp[((n0 + i < N) ? n0 + i : N - 1) * V];
+            for (int i = 0; i < U; i++) hc[i] = hp[((n0 + i < N) ? n0 + i : N - 1) * V];
         }
-        const int cnt = n0 + U <= N ? U : (int)(N - n0);  // (wave-uniform; a ragged last chunk goes out sample by sample)
+        const int cnt = n0 + U <= N ? U : (int)(N - n0);  // (wave-uniform, mxg_stream.h)
         double y[U];
         unsigned bits = 0;
         if (w_zx) {
@@ -128,7 +107,7 @@ __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
                 y[i] = bit ? 1.0 : 0.0;
                 if (i + 1 == cnt) break;
             }
-            if (ozx) ana_emit<PX>(ozx, V, y, cnt, A.px_store);
+            if (ozx) emit_rows<PX>(ozx, V, y, cnt, A.px_store);
         }
         if (w_zcr) {
 #pragma unroll
@@ -136,7 +115,7 @@ __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
                 y[i] = ana_zcr_step(z, (bits >> i & 1) != 0);
                 if (i + 1 == cnt) break;
             }
-            ana_emit<PX>(ozc, V, y, cnt, A.px_store);
+            emit_rows<PX>(ozc, V, y, cnt, A.px_store);
         }
         if (w_env) {
 #pragma unroll
@@ -144,7 +123,7 @@ __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
                 y[i] = ana_follow<double>(env, att, rel, xc[i]);
                 if (i + 1 == cnt) break;
             }
-            ana_emit<PX>(oen, V, y, cnt, A.px_store);
+            emit_rows<PX>(oen, V, y, cnt, A.px_store);
         }
         if (w_sah) {
 #pragma unroll
@@ -152,7 +131,7 @@ __global__ void __launch_bounds__(256) analysis_kernel(AnaArgs A) {
                 y[i] = ana_sah(phase, held, xc[i], hold_ps ? ana_hold_samples(hc[i], A.sr) : hold);
                 if (i + 1 == cnt) break;
             }
-            ana_emit<PX>(osh, V, y, cnt, A.px_store);
+            emit_rows<PX>(osh, V, y, cnt, A.px_store);
         }
     }
     if (!live) return;  // a shadow lane owns no state
@@ -222,9 +201,7 @@ int mxg_analysis_render(size_t V, size_t N, const double *d_in, int want, double
     if (int s = ensure_init()) return s;  // (after the argument checks: a refused call says why on a machine without a device too)
     if (V == 0 || N == 0) return MXG_OK;
     hipStream_t st = resolve_stream(stream);
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
-    if (V <= 16384) block = 64;
+    const int block = voice_block(V, true);
     double *outs[4] = {(want & MXG_ANA_WANT_ZX) ? d_zx : nullptr, (want & MXG_ANA_WANT_ZCR) ? d_zcr : nullptr,
                        (want & MXG_ANA_WANT_ENV) ? d_env_out : nullptr, (want & MXG_ANA_WANT_SAH) ? d_sah : nullptr};
     double *first = nullptr;
@@ -238,10 +215,8 @@ int mxg_analysis_render(size_t V, size_t N, const double *d_in, int want, double
     const AnaArgs A = {V, N, d_in, want, d_prev_x, d_window, d_zring, (int)cap, d_zpos, d_zcount, d_overflow, d_attack, d_release,
                        d_env, d_hold_ms, hold_per_sample ? 1 : 0, d_sah_phase, d_sah_value, outs[0], outs[1], outs[2], outs[3],
                        (double)settings().sampleRate, px};
-    const dim3 grid((unsigned)((V + block - 1) / block));
     KernelTimer kt("analysis_kernel", st);
-    if (px) hipLaunchKernelGGL((analysis_kernel<true>), grid, dim3(block), 0, st, A);
-    else hipLaunchKernelGGL((analysis_kernel<false>), grid, dim3(block), 0, st, A);
+    with_bools([&](auto PX) { hipLaunchKernelGGL((analysis_kernel<PX.value>), voice_grid(V, block), dim3(block), 0, st, A); }, px != 0);
     return check_hip(hipGetLastError(), "analysis_kernel launch");
 }
 

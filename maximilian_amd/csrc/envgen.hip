@@ -13,7 +13,7 @@
 #include <math.h>
 
 #include "mxg_common.h"
-#include "mxg_gate.h"
+#include "mxg_stream.h"
 #include "mxg_envgen.h"
 
 namespace mxg {
@@ -49,17 +49,15 @@ __global__ void __launch_bounds__(256) envgen_kernel(EgArgs A, const double *__r
     __syncthreads();
     const size_t V = A.V, N = A.N;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if ((gid & ~(size_t)63) >= V) return;  // the whole wavefront is past the bank
-    // surplus lanes shadow voice V-1 (mxg_gate.h); with pair rows the last PAIR of voices, parity kept (voice_kernel, voice.hip)
-    const size_t v = PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    if (bank_wave_idle(gid, V)) return;
+    const size_t v = bank_voice<PX>(gid, V);
     constexpr int WAITING = EG_WAITING, HOLDING = EG_HOLDING;
     double envval = A.dst[v], currentlevel = A.dst[V + v];
     double tprev = A.dst[2 * V + v], hprev = A.dst[3 * V + v], rprev = A.dst[4 * V + v];
     long long phase = A.ist[v], counter = A.ist[3 * V + v];
     long long i_state = A.ist[V + v], i_nxc = A.ist[2 * V + v];
     long long i_tf = A.ist[4 * V + v], i_hf = A.ist[5 * V + v], i_rf = A.ist[6 * V + v];
-    // consume every prologue load here: a use inside the loop would be a counted wait the compiler has to place
-    // conservatively (vmcnt(4..8) on every chunk = draining the output stores, which share the counter)
+    // consume every prologue load here (mxg_stream.h)
     asm volatile("" : "+v"(envval), "+v"(currentlevel), "+v"(tprev), "+v"(hprev), "+v"(rprev), "+v"(phase), "+v"(counter));
     asm volatile("" : "+v"(i_state), "+v"(i_nxc), "+v"(i_tf), "+v"(i_hf), "+v"(i_rf));
     int state = (int)i_state;
@@ -75,11 +73,7 @@ __global__ void __launch_bounds__(256) envgen_kernel(EgArgs A, const double *__r
     int gflags = 0;             // ... and whether the trigger (bit 0) / its negation (bit 1) crosses zero upwards inside chunk j
     const auto positive = [](double t) { return t > 0; };
     if constexpr (TPV) {
-#pragma unroll
-        for (int i = 0; i < U; i++) {
-            const size_t m = (size_t)i < N ? (size_t)i : N - 1;
-            tn[i] = tp[m * V];
-        }
+        rows_first(tn, tp, V, N);
     } else {
         gate_group_load(gcur, trig_in, N, 0, positive);
         const EgCross xg = envgen_cross<U>(gcur.g);
@@ -89,14 +83,7 @@ __global__ void __launch_bounds__(256) envgen_kernel(EgArgs A, const double *__r
     EgRow row = envgen_row(s_tab, A.nstages, phase);  // the stage row of `phase`, re-read when the stage machine has run
     for (size_t n0 = 0; n0 < N; n0 += U) {
         double tc[U];
-        if constexpr (TPV) {
-#pragma unroll
-            for (int i = 0; i < U; i++) {
-                tc[i] = tn[i];
-                const size_t m = (n0 + U + i < N) ? n0 + U + i : N - 1;  // clamped prefetch, a chunk ahead of the stores
-                tn[i] = tp[m * V];
-            }
-        }
+        if constexpr (TPV) rows_next(tc, tn, tp, V, N, n0);
         // Two steady states in which nothing but a detector's previousValue moves and envval is simply repeated:
         // HOLDING while the trigger stays positive (no negative zero crossing, H:2334-2341) and WAITING while it
         // stays <= 0, or stays positive after a positive sample (no trigger either way, H:2281 / onZX H:569-579).  With a shared gate the test is one readlane plus one ballot per chunk.
@@ -224,20 +211,14 @@ int mxg_envgen_render(size_t V, size_t N, const double *d_trig, int tpv, const d
     MXG_REQUIRE(d_trig && d_stages && d_dst && d_ist && d_out, "null device pointer");
     MXG_REQUIRE(nstages >= 1 && nstages <= kMaxStages, "nstages out of [1, 32]");
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
+    const int block = voice_block(V);
     // the output stream (knob rw_store, rw_store_choice in mxg_common.h: automatic = pair rows of non-temporal stores from 98 304 voices)
     const EgArgs A = {V, N, d_trig, tpv, nstages, loop, retrigger, d_stages, d_dst, d_ist, d_out, rw_store_choice(V, N, d_out, RW_ENVGEN)};
-    const dim3 grid((unsigned)((V + block - 1) / block));
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("envgen_kernel", st);
-    if (tpv) {
-        if (A.px_store) hipLaunchKernelGGL((envgen_kernel<true, true>), grid, dim3(block), 0, st, A, d_trig, d_out);
-        else hipLaunchKernelGGL((envgen_kernel<true, false>), grid, dim3(block), 0, st, A, d_trig, d_out);
-    } else {
-        if (A.px_store) hipLaunchKernelGGL((envgen_kernel<false, true>), grid, dim3(block), 0, st, A, d_trig, d_out);
-        else hipLaunchKernelGGL((envgen_kernel<false, false>), grid, dim3(block), 0, st, A, d_trig, d_out);
-    }
+    with_bools([&](auto TPV, auto PX) {
+        hipLaunchKernelGGL((envgen_kernel<TPV.value, PX.value>), voice_grid(V, block), dim3(block), 0, st, A, d_trig, d_out);
+    }, tpv != 0, A.px_store != 0);
     return check_hip(hipGetLastError(), "envgen_kernel launch");
 }
 

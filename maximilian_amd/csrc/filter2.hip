@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "mxg_common.h"
+#include "mxg_stream.h"
 
 namespace mxg {
 namespace {
@@ -157,9 +158,7 @@ int mxg_filter2_render(int kind, size_t V, size_t N, const double *d_in, const d
     MXG_REQUIRE(kind >= 0 && kind <= 2, "kind must be 0 (maxiDCBlocker), 1 (maxiSVF) or 2 (maxiBiquad)");
     MXG_REQUIRE(d_in && d_coef && d_st && d_out, "null device pointer");
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
-    const dim3 grid((unsigned)((V + block - 1) / block));
+    const dim3 block(voice_block(V)), grid = voice_grid(V, block.x);
     hipStream_t st = resolve_stream(stream);
     if (scan_applies(V, N)) return scan_filter_launch(kind, V, N, d_in, d_coef, d_st, d_out, st);  // tolerance mode (scan.hip)
     // 16-byte pair-row streams (knob rw_store: 0 automatic, 1 off, 2 / 3 / 4 plain / write-through / non-temporal stores)
@@ -168,19 +167,21 @@ int mxg_filter2_render(int kind, size_t V, size_t N, const double *d_in, const d
     if (rw == 0) rw = (V * N * sizeof(double) >= ((size_t)64 << 20)) ? 3 : 1;
     if (rw >= 2 && pairs_ok) {
         KernelTimer kt("filter2_kernel", st);
-#define MXG_F2P(K)                                                                                                   \
-    if (rw == 2) hipLaunchKernelGGL((filter2_pairs_kernel<K, 0>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out); \
-    else if (rw == 3) hipLaunchKernelGGL((filter2_pairs_kernel<K, 2>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out); \
-    else hipLaunchKernelGGL((filter2_pairs_kernel<K, 1>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out);
-        if (kind == 0) { MXG_F2P(0) } else if (kind == 1) { MXG_F2P(1) } else { MXG_F2P(2) }
-#undef MXG_F2P
+        const auto launch = [&](auto K) {  // (the last argument: store2's flavour, mxg_common.h)
+            if (rw == 2) hipLaunchKernelGGL((filter2_pairs_kernel<K.value, 0>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out);
+            else if (rw == 3) hipLaunchKernelGGL((filter2_pairs_kernel<K.value, 2>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out);
+            else hipLaunchKernelGGL((filter2_pairs_kernel<K.value, 1>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out);
+        };
+        if (kind == 0) launch(std::integral_constant<int, 0>{});
+        else if (kind == 1) launch(std::integral_constant<int, 1>{});
+        else launch(std::integral_constant<int, 2>{});
         return check_hip(hipGetLastError(), "filter2_pairs_kernel launch");
     }
     KernelTimer kt("filter2_kernel", st);
     switch (kind) {
-        case 0: hipLaunchKernelGGL((filter2_kernel<0>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out); break;
-        case 1: hipLaunchKernelGGL((filter2_kernel<1>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out); break;
-        default: hipLaunchKernelGGL((filter2_kernel<2>), grid, dim3(block), 0, st, V, N, d_in, d_coef, d_st, d_out); break;
+        case 0: hipLaunchKernelGGL((filter2_kernel<0>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out); break;
+        case 1: hipLaunchKernelGGL((filter2_kernel<1>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out); break;
+        default: hipLaunchKernelGGL((filter2_kernel<2>), grid, block, 0, st, V, N, d_in, d_coef, d_st, d_out); break;
     }
     return check_hip(hipGetLastError(), "filter2_kernel launch");
 }

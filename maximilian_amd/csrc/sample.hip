@@ -18,6 +18,7 @@
 // sizes of the configs); per sample a lane gathers 1-4 neighbouring doubles (K5, 8 B out +
 // gather).  The buffer must be valid on [-4, len+5] with zero guards (mxg_sample_upload's layout, mxg_smp.h).
 #include "mxg_common.h"
+#include "mxg_stream.h"
 #include "mxg_pace.h"
 #include "mxg_advance.h"
 #include "mxg_smp.h"
@@ -841,7 +842,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RING ?
     if (writer && part_wait(part_ctr, psync)) A.position[v] = s.pos;
 }
 
-inline dim3 grid_for(size_t V, int block) { return dim3((unsigned)((V + block - 1) / block)); }
 
 // time parts for a block-constant *AtSpeed launch: the kernel keeps three wavefronts per SIMD resident (~160 VGPRs); two rounds
 // of them measured best at 65 536 voices (69 us with 6 parts against 76 with 4 and 84 with 3), each part >= 32 samples
@@ -959,8 +959,7 @@ int mxg_delay_render(int mode, size_t V, size_t N, const double *d_in, const int
     MXG_REQUIRE(mode == 0 || d_position, "dlFromPosition needs d_position");
     MXG_REQUIRE(cap > 0 && cap <= 0x7fffffff, "cap must be in 1 .. 2^31-1");
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;  // delay_kernel is compiled for <= 256 lanes per workgroup
+    const int block = voice_block(V);
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("delay_kernel", st);
     // 16-byte pair-row input / output streams for dl (knob rw_store, rw_store_choice in mxg_common.h: automatic = non-temporal stores for
@@ -968,7 +967,7 @@ int mxg_delay_render(int mode, size_t V, size_t N, const double *d_in, const int
     const bool pairs_ok = mode == 0 && !(((uintptr_t)d_in) & 15);
     const int rw = pairs_ok ? 1 + rw_store_choice(V, N, d_out, RW_WRITE_ONLY) : 1;  // (1 = 8-byte streams, 2 / 3 / 4 as the knob)
 #define MXG_DL(M, X)                                                                                              \
-    hipLaunchKernelGGL((delay_kernel<M, X>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_size, d_feedback, \
+    hipLaunchKernelGGL((delay_kernel<M, X>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_size, d_feedback, \
                        d_position, d_mem, (int)cap, d_phase, d_out)
     if (mode == 1) MXG_DL(1, 0);
     else if (!pairs_ok || rw < 2) MXG_DL(0, 0);
@@ -1016,13 +1015,12 @@ int mxg_sample_render(int mode, size_t V, size_t N, const double *d_samples, siz
     MXG_REQUIRE(!(mode == 3 || mode == 6) || d_end, "mode needs d_end");
     if (V == 0 || N == 0) return MXG_OK;
     const size_t q = settings().sampleRate / (size_t)mySampleRate;  // integer division, C:1070
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;  // sample_kernel is compiled for <= 256 lanes per workgroup
+    const int block = voice_block(V);
     hipStream_t st = resolve_stream(stream);
     SmpArgs A = {V, N, d_samples, len, (double)q, (double)settings().sampleRate, d_a, nullptr,
                        d_start, d_end, d_position, nullptr, nullptr, d_out, rw_store_choice(V, N, d_out, RW_WRITE_ONLY), 0u, nullptr};
     const bool xmod = mode >= 4 && aps;
-    const dim3 grid = grid_for(V, block);
+    const dim3 grid = voice_grid(V, block);
     {
         // the paced schedule (mxg_pace.h; knob smp_pace: 0 automatic, 1 never, >= 2 a fixed period in ticks of 10 ns per 8 samples and
         // wavefront): play() -- whose whole-chunk path is a pure store stream -- at the store-bound bank sizes, on the controller
@@ -1095,13 +1093,12 @@ int mxg_sample_render_trig(int mode, size_t V, size_t N, const double *d_samples
     MXG_REQUIRE(mode != 12 || d_p1, "playOnZXAtSpeedBetweenPoints needs d_p1 (length)");
     if (V == 0 || N == 0) return MXG_OK;
     const size_t q = settings().sampleRate / (size_t)mySampleRate;  // integer division, C:1070
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
+    const int block = voice_block(V);
     hipStream_t st = resolve_stream(stream);
     const SmpArgs A = {V, N, d_samples, len, (double)q, (double)settings().sampleRate, d_a, d_trig,
                        d_p0, d_p1, d_position, d_tprev, d_tfirst, d_out, rw_store_choice(V, N, d_out, RW_WRITE_ONLY), 0u, nullptr};
     const bool xmod = aps != 0;
-    const dim3 grid = grid_for(V, block);
+    const dim3 grid = voice_grid(V, block);
     switch (mode) {
         case 9: launch_sample<9>(xmod, grid, dim3(block), st, A); break;
         case 10: launch_sample<10>(xmod, grid, dim3(block), st, A); break;

@@ -9,11 +9,11 @@
 // value and gate blocks are what mxg_envgen_render (tpv = 1) and mxg_osc_render (fps = 1) read, so a whole bank is sequenced
 // without a host array per block.  seq_signal_kernel (mxg_seq_signal) drives the same step functions from [N][V] signals.
 //
-// Shape, as envgen.hip: one lane = one voice, chunks of 8 samples, surplus lanes shadow the last voice (pair), whole chunks leave
+// Shape (mxg_stream.h): one lane = one voice, chunks of 8 samples, surplus lanes shadow the last voice (pair), whole chunks leave
 // through emit_chunk (8-byte stores or 16-byte pair rows), prologue loads are consumed before the loop, the boundary and value
 // tables sit in LDS.  No scratch.
 #include "mxg_common.h"
-#include "mxg_gate.h"
+#include "mxg_stream.h"
 #include "mxg_seq.h"
 
 namespace mxg {
@@ -68,8 +68,8 @@ __global__ void __launch_bounds__(256) seq_kernel(SeqArgs A, const double *__res
     seq_load_tabs(A.pat, A.val, s_seq, tpat, tval, lpat, lval);
     const size_t V = A.V, N = A.N;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if ((gid & ~(size_t)63) >= V) return;  // the whole wavefront is past the bank
-    const size_t v = PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    if (bank_wave_idle(gid, V)) return;
+    const size_t v = bank_voice<PX>(gid, V);
     const int want = A.want;
     const bool w_val = (want & (MXG_SEQ_WANT_VALUES | MXG_SEQ_WANT_STEP)) != 0, w_step = (want & MXG_SEQ_WANT_STEP) != 0;
     const bool w_gate = (want & MXG_SEQ_WANT_GATE) != 0;
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) seq_kernel(SeqArgs A, const double *__res
     double prevPhase = A.dst[v], sprev = A.dst[V + v], sindex = A.dst[2 * V + v], pprev = A.dst[3 * V + v], phold = A.dst[4 * V + v];
     long long i_rf = A.ist[v], counter = A.ist[V + v], lov = A.ist[2 * V + v];
     long long i_sf = A.ist[3 * V + v], i_sfirst = A.ist[4 * V + v], i_pf = A.ist[5 * V + v];
-    // consume every prologue load here (envgen.hip): a use inside the loop would be a counted wait that drains the output stores
+    // consume every prologue load here (mxg_stream.h)
     asm volatile("" : "+v"(clk), "+v"(freq), "+v"(prevPhase), "+v"(sprev), "+v"(sindex), "+v"(pprev), "+v"(phold));
     asm volatile("" : "+v"(i_rf), "+v"(counter), "+v"(lov), "+v"(i_sf), "+v"(i_sfirst), "+v"(i_pf), "+v"(c.step), "+v"(c.hold));
     SeqRatio r = {prevPhase, i_rf != 0, counter, lov};
@@ -102,24 +102,11 @@ __global__ void __launch_bounds__(256) seq_kernel(SeqArgs A, const double *__res
     constexpr int U = 8;
     const double *__restrict__ pp = CLK == 1 ? phase_in + v : phase_in;
     double tn[U];
-    if constexpr (CLK == 1) {
-#pragma unroll
-        for (int i = 0; i < U; i++) {
-            const size_t m = (size_t)i < N ? (size_t)i : N - 1;
-            tn[i] = pp[m * V];
-        }
-    }
+    if constexpr (CLK == 1) rows_first(tn, pp, V, N);
     double *ot = A.trig ? A.trig + v : nullptr, *ov = w_val ? A.valo + v : nullptr, *og = w_gate ? A.gate + v : nullptr;
     for (size_t n0 = 0; n0 < N; n0 += U) {
         double tc[U];
-        if constexpr (CLK == 1) {
-#pragma unroll
-            for (int i = 0; i < U; i++) {
-                tc[i] = tn[i];
-                const size_t m = (n0 + U + i < N) ? n0 + U + i : N - 1;  // clamped prefetch, a chunk ahead of the stores
-                tn[i] = pp[m * V];
-            }
-        }
+        if constexpr (CLK == 1) rows_next(tc, tn, pp, V, N, n0);
         const bool whole = n0 + U <= N;  // (wave-uniform; a ragged last chunk goes out sample by sample)
         double xt[U], xv[U], xg[U];
 #pragma unroll
@@ -187,8 +174,8 @@ __global__ void __launch_bounds__(256) seq_signal_kernel(SigArgs A, const double
     seq_load_tabs(kTab ? A.val : none, none, s_seq, tval, tnone, lval, lnone);
     const size_t V = A.V, N = A.N;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if ((gid & ~(size_t)63) >= V) return;
-    const size_t v = PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    if (bank_wave_idle(gid, V)) return;
+    const size_t v = bank_voice<PX>(gid, V);
     const double *values = nullptr;
     int vlen = 1;
     if constexpr (kTab) {
@@ -254,12 +241,6 @@ __global__ void __launch_bounds__(256) seq_signal_kernel(SigArgs A, const double
 bool tabs_ok(const double *tab, const int32_t *len, size_t P, size_t L) { return tab && len && P >= 1 && L >= 1 && P <= 65536 && L <= 65536; }
 size_t tabs_bytes(size_t P, size_t L) { return P * L * sizeof(double) + P * sizeof(int); }
 
-template <int KIND>
-void launch_signal(bool px, dim3 grid, dim3 block, size_t lds, hipStream_t st, const SigArgs &A, const double *in, double *out) {
-    if (px) hipLaunchKernelGGL((seq_signal_kernel<KIND, true>), grid, block, lds, st, A, in, out);
-    else hipLaunchKernelGGL((seq_signal_kernel<KIND, false>), grid, block, lds, st, A, in, out);
-}
-
 }  // namespace
 }  // namespace mxg
 
@@ -302,27 +283,20 @@ int mxg_seq_render(size_t V, size_t N, const double *d_freq, double *d_clk, cons
     MXG_REQUIRE(lds <= (size_t)kSeqLdsBytes, "pattern and value tables exceed 48 KB");
     if (int s = ensure_init()) return s;  // (after the argument checks: a refused call says why on a machine without a device too)
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
+    const dim3 block(voice_block(V)), grid = voice_grid(V, block.x);
     double *first = d_trig ? d_trig : (d_val ? d_val : d_gate);
     int px = rw_store_choice(V, N, first, RW_WRITE_ONLY);
     if (((uintptr_t)d_trig | (uintptr_t)d_val | (uintptr_t)d_gate) & 15) px = 0;
     const double sr = (double)settings().sampleRate;
     const SeqArgs A = {V, N, d_freq, d_clk, phase_pv, {d_norm, d_len, (int)P, (int)L}, vt, d_pat, d_vpat, d_step, d_hold,
                        d_dst, d_ist, d_trig, d_val, d_gate, want, sr, 1.0 / sr, px};
-    const dim3 grid((unsigned)((V + block - 1) / block));
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("seq_kernel", st);
-    const int clk = d_freq ? 0 : (phase_pv ? 1 : 2);
-#define MXG_SEQ_LAUNCH(C)                                                                                      \
-    do {                                                                                                       \
-        if (px) hipLaunchKernelGGL((seq_kernel<C, true>), grid, dim3(block), lds, st, A, d_phase);             \
-        else hipLaunchKernelGGL((seq_kernel<C, false>), grid, dim3(block), lds, st, A, d_phase);               \
-    } while (0)
-    if (clk == 0) MXG_SEQ_LAUNCH(0);
-    else if (clk == 1) MXG_SEQ_LAUNCH(1);
-    else MXG_SEQ_LAUNCH(2);
-#undef MXG_SEQ_LAUNCH
+    with_bools([&](auto PX) {
+        if (d_freq) hipLaunchKernelGGL((seq_kernel<0, PX.value>), grid, block, lds, st, A, d_phase);
+        else if (phase_pv) hipLaunchKernelGGL((seq_kernel<1, PX.value>), grid, block, lds, st, A, d_phase);
+        else hipLaunchKernelGGL((seq_kernel<2, PX.value>), grid, block, lds, st, A, d_phase);
+    }, px != 0);
     return check_hip(hipGetLastError(), "seq_kernel launch");
 }
 
@@ -344,20 +318,20 @@ int mxg_seq_signal(int kind, size_t V, size_t N, const double *d_in, const doubl
     }
     if (int s = ensure_init()) return s;  // (after the argument checks: a refused call says why on a machine without a device too)
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
+    const dim3 block(voice_block(V)), grid = voice_grid(V, block.x);
     int px = rw_store_choice(V, N, d_out, RW_READ_WRITE);
     const SigArgs A = {V, N, d_in2, vt, d_vpat, d_par, d_dst, d_ist, px};
-    const dim3 grid((unsigned)((V + block - 1) / block));
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("seq_signal_kernel", st);
-    switch (kind) {
-        case MXG_SEQ_ONZX: launch_signal<MXG_SEQ_ONZX>(px != 0, grid, dim3(block), lds, st, A, d_in, d_out); break;
-        case MXG_SEQ_COUNTER: launch_signal<MXG_SEQ_COUNTER>(px != 0, grid, dim3(block), lds, st, A, d_in, d_out); break;
-        case MXG_SEQ_STEP: launch_signal<MXG_SEQ_STEP>(px != 0, grid, dim3(block), lds, st, A, d_in, d_out); break;
-        case MXG_SEQ_INDEX: launch_signal<MXG_SEQ_INDEX>(px != 0, grid, dim3(block), lds, st, A, d_in, d_out); break;
-        default: launch_signal<MXG_SEQ_ZXTOPULSE>(px != 0, grid, dim3(block), lds, st, A, d_in, d_out); break;
-    }
+    with_bools([&](auto PX) {
+        switch (kind) {
+            case MXG_SEQ_ONZX: hipLaunchKernelGGL((seq_signal_kernel<MXG_SEQ_ONZX, PX.value>), grid, block, lds, st, A, d_in, d_out); break;
+            case MXG_SEQ_COUNTER: hipLaunchKernelGGL((seq_signal_kernel<MXG_SEQ_COUNTER, PX.value>), grid, block, lds, st, A, d_in, d_out); break;
+            case MXG_SEQ_STEP: hipLaunchKernelGGL((seq_signal_kernel<MXG_SEQ_STEP, PX.value>), grid, block, lds, st, A, d_in, d_out); break;
+            case MXG_SEQ_INDEX: hipLaunchKernelGGL((seq_signal_kernel<MXG_SEQ_INDEX, PX.value>), grid, block, lds, st, A, d_in, d_out); break;
+            default: hipLaunchKernelGGL((seq_signal_kernel<MXG_SEQ_ZXTOPULSE, PX.value>), grid, block, lds, st, A, d_in, d_out); break;
+        }
+    }, px != 0);
     return check_hip(hipGetLastError(), "seq_signal_kernel launch");
 }
 

@@ -11,13 +11,13 @@
 // remainder of the stride.  HBM per element: 8 B in + 8 B out (+ 8 B per per-sample parameter); xfade 8 B + C * 24 B; select
 // 8 B index + 8 (Select) or 16 (SelectX) B of values + 8 B out.
 //
-// line_kernel is a state machine and takes envgen.hip's shape: one lane = one voice, chunks of 8 samples, surplus lanes shadow
+// line_kernel is a state machine and takes the streaming shape of mxg_stream.h: one lane = one voice, chunks of 8 samples, surplus lanes shadow
 // the last voice (pair) and store no state, whole chunks leave through emit_chunk, the trigger is requested a chunk ahead.
 // No scratch in any instantiation.
 #include <math.h>
 
 #include "mxg_common.h"
-#include "mxg_gate.h"
+#include "mxg_stream.h"
 #include "mxg_shaper.h"
 
 namespace mxg {
@@ -265,12 +265,12 @@ template <bool TB, bool PX>
 __global__ void __launch_bounds__(256) line_kernel(LineArgs A, const double *__restrict__ trig_in, double *__restrict__ out_ptr) {
     const size_t V = A.V, N = A.N;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if ((gid & ~(size_t)63) >= V) return;  // the whole wavefront is past the bank
+    if (bank_wave_idle(gid, V)) return;
     const bool live = gid < V;
-    const size_t v = PX ? (live ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    const size_t v = bank_voice<PX>(gid, V);
     double p_start = A.par[v], p_end = A.par[V + v], p_inc = A.par[2 * V + v], p_one = A.par[3 * V + v], p_en = A.par[4 * V + v];
     double s_value = A.st[v], s_last = A.st[V + v], s_trig = A.st[2 * V + v], s_done = A.st[3 * V + v];
-    // consume every prologue load here (envgen.hip): a use inside the loop would be a counted wait that drains the output stores
+    // consume every prologue load here (mxg_stream.h)
     asm volatile("" : "+v"(p_start), "+v"(p_end), "+v"(p_inc), "+v"(p_one), "+v"(p_en));
     asm volatile("" : "+v"(s_value), "+v"(s_last), "+v"(s_trig), "+v"(s_done));
     const LinePar P = {p_start, p_end, p_inc, p_one != 0.0, p_en != 0.0};
@@ -279,42 +279,23 @@ __global__ void __launch_bounds__(256) line_kernel(LineArgs A, const double *__r
     const double *__restrict__ tp = TB ? trig_in + v : nullptr;
     double *op = out_ptr + v;
     double tn[U];
-    if constexpr (TB) {
-#pragma unroll
-        for (int i = 0; i < U; i++) {
-            const size_t mm = (size_t)i < N ? (size_t)i : N - 1;
-            tn[i] = tp[mm * V];
-        }
-    }
+    if constexpr (TB) rows_first(tn, tp, V, N);
     for (size_t n0 = 0; n0 < N; n0 += U) {
         double tc[U];
+        if constexpr (TB) {
+            rows_next(tc, tn, tp, V, N, n0);
+        } else {
 #pragma unroll
-        for (int i = 0; i < U; i++) {
-            if constexpr (TB) {
-                tc[i] = tn[i];
-                const size_t mm = (n0 + U + i < N) ? n0 + U + i : N - 1;  // clamped prefetch, a chunk ahead of the stores
-                tn[i] = tp[mm * V];
-            } else {
-                tc[i] = A.trig_const;
-            }
+            for (int i = 0; i < U; i++) tc[i] = A.trig_const;
         }
-        const int cnt = n0 + U <= N ? U : (int)(N - n0);  // (wave-uniform; a ragged last chunk goes out sample by sample)
+        const int cnt = n0 + U <= N ? U : (int)(N - n0);  // (wave-uniform, mxg_stream.h)
         double y[U];
 #pragma unroll
         for (int i = 0; i < U; i++) {
             y[i] = shp_line(S, P, tc[i]);
             if (i + 1 == cnt) break;
         }
-        if (cnt == U) {
-            emit_chunk<PX>(op, V, y, A.px_store);
-        } else {
-#pragma unroll
-            for (int i = 0; i < U; i++) {
-                if (i >= cnt) break;
-                *op = y[i];
-                op += V;
-            }
-        }
+        emit_rows<PX>(op, V, y, cnt, A.px_store);
     }
     if (!live) return;  // a shadow lane owns no state
     A.st[v] = S.value;
@@ -341,14 +322,9 @@ unsigned flat_grid(const FlatGeom &g, bool vec) {
 
 template <int MODE>
 void shape_launch(bool ps, bool vec, unsigned grid, hipStream_t st, const ShapeArgs &A) {
-    const dim3 g(grid), b(kFlatBlock);
-    if (ps) {
-        if (vec) hipLaunchKernelGGL((shape_kernel<MODE, true, true>), g, b, 0, st, A);
-        else hipLaunchKernelGGL((shape_kernel<MODE, true, false>), g, b, 0, st, A);
-    } else {
-        if (vec) hipLaunchKernelGGL((shape_kernel<MODE, false, true>), g, b, 0, st, A);
-        else hipLaunchKernelGGL((shape_kernel<MODE, false, false>), g, b, 0, st, A);
-    }
+    with_bools([&](auto PS, auto VEC) {
+        hipLaunchKernelGGL((shape_kernel<MODE, PS.value, VEC.value>), dim3(grid), dim3(kFlatBlock), 0, st, A);
+    }, ps, vec);
 }
 
 }  // namespace
@@ -430,13 +406,7 @@ int mxg_xfade_render(size_t C, size_t V, size_t N, const double *d_ch1, const do
     const dim3 grid(flat_grid(A.g, vec)), block(kFlatBlock);
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("xfade_kernel", st);
-    if (ps) {
-        if (vec) hipLaunchKernelGGL((xfade_kernel<true, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((xfade_kernel<true, false>), grid, block, 0, st, A);
-    } else {
-        if (vec) hipLaunchKernelGGL((xfade_kernel<false, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((xfade_kernel<false, false>), grid, block, 0, st, A);
-    }
+    with_bools([&](auto PS, auto VEC) { hipLaunchKernelGGL((xfade_kernel<PS.value, VEC.value>), grid, block, 0, st, A); }, ps, vec);
     return check_hip(hipGetLastError(), "xfade_kernel launch");
 }
 
@@ -455,17 +425,9 @@ int mxg_select_render(int interpolate, size_t K, size_t V, size_t N, const doubl
     const dim3 grid(flat_grid(A.g, vec)), block(kFlatBlock);
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("select_kernel", st);
-    const int which = (interpolate ? 4 : 0) | (values_are_signals ? 2 : 0) | (vec ? 1 : 0);
-    switch (which) {
-        case 0: hipLaunchKernelGGL((select_kernel<false, false, false>), grid, block, 0, st, A); break;
-        case 1: hipLaunchKernelGGL((select_kernel<false, false, true>), grid, block, 0, st, A); break;
-        case 2: hipLaunchKernelGGL((select_kernel<false, true, false>), grid, block, 0, st, A); break;
-        case 3: hipLaunchKernelGGL((select_kernel<false, true, true>), grid, block, 0, st, A); break;
-        case 4: hipLaunchKernelGGL((select_kernel<true, false, false>), grid, block, 0, st, A); break;
-        case 5: hipLaunchKernelGGL((select_kernel<true, false, true>), grid, block, 0, st, A); break;
-        case 6: hipLaunchKernelGGL((select_kernel<true, true, false>), grid, block, 0, st, A); break;
-        default: hipLaunchKernelGGL((select_kernel<true, true, true>), grid, block, 0, st, A); break;
-    }
+    with_bools([&](auto X, auto SIG, auto VEC) {
+        hipLaunchKernelGGL((select_kernel<X.value, SIG.value, VEC.value>), grid, block, 0, st, A);
+    }, interpolate != 0, values_are_signals != 0, vec);
     return check_hip(hipGetLastError(), "select_kernel launch");
 }
 
@@ -476,20 +438,13 @@ int mxg_line_render(size_t V, size_t N, const double *d_trig, double trig_const,
     MXG_REQUIRE(d_out, "d_out is null");
     if (int s = ensure_init()) return s;
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;
-    if (V <= 16384) block = 64;
+    const int block = voice_block(V, true);
     const LineArgs A = {V, N, trig_const, d_par, d_st, rw_store_choice(V, N, d_out, d_trig ? RW_READ_WRITE : RW_WRITE_ONLY)};
-    const dim3 grid((unsigned)((V + block - 1) / block));
     hipStream_t st = resolve_stream(stream);
     KernelTimer kt("line_kernel", st);
-    if (d_trig) {
-        if (A.px_store) hipLaunchKernelGGL((line_kernel<true, true>), grid, dim3(block), 0, st, A, d_trig, d_out);
-        else hipLaunchKernelGGL((line_kernel<true, false>), grid, dim3(block), 0, st, A, d_trig, d_out);
-    } else {
-        if (A.px_store) hipLaunchKernelGGL((line_kernel<false, true>), grid, dim3(block), 0, st, A, d_trig, d_out);
-        else hipLaunchKernelGGL((line_kernel<false, false>), grid, dim3(block), 0, st, A, d_trig, d_out);
-    }
+    with_bools([&](auto TB, auto PX) {
+        hipLaunchKernelGGL((line_kernel<TB.value, PX.value>), voice_grid(V, block), dim3(block), 0, st, A, d_trig, d_out);
+    }, d_trig != nullptr, A.px_store != 0);
     return check_hip(hipGetLastError(), "line_kernel launch");
 }
 

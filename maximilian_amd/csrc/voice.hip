@@ -21,6 +21,7 @@
 
 #include "maxi_tables.h"
 #include "mxg_common.h"
+#include "mxg_stream.h"
 #include "mxg_env.h"
 #include "mxg_lanefold.h"
 #include "mxg_pace.h"
@@ -343,7 +344,7 @@ __global__ void __launch_bounds__(256) env_kernel(size_t V, size_t N, const doub
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if ((gid & ~(size_t)63) >= V) return;  // the whole wavefront is past the bank
     // (pair rows: the surplus lanes of the last wavefront shadow the last PAIR of voices, parity kept: voice_kernel)
-    const size_t v = PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    const size_t v = bank_voice<(PX != 0)>(gid, V);
     constexpr int PST = PX == 2 ? 2 : (PX == 3 ? 1 : 0);
     Env e;
     env_load(e, V, v, par, holdtime, dst, ist);
@@ -582,7 +583,7 @@ __global__ void __launch_bounds__(MIX ? 512 : 256) voice_kernel(size_t V, size_t
     }
     // (pair rows: the surplus lanes of the last wavefront shadow the last PAIR of voices, parity kept, so that they exchange
     // among themselves and store the values their owners store, to the same addresses)
-    const size_t v = PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
+    const size_t v = bank_voice<(PX != 0)>(gid, V);
     double phase = ost[v], hold = ost[V + v];
     Flt f = {fst[v], fst[V + v], fst[2 * V + v], fst[3 * V + v], fst[4 * V + v]};
     Env e;
@@ -966,7 +967,6 @@ __global__ void __launch_bounds__(MIX ? 512 : 256) voice_kernel(size_t V, size_t
     if ((threadIdx.x & (MIX ? 255 : ~0u)) == 0 && (!MIX || threadIdx.x < 256)) pc.finish(pace_ctl, pace_arg, (unsigned)wg, gridDim.x);
 }
 
-inline dim3 grid_for(size_t V, int block) { return dim3((unsigned)((V + block - 1) / block)); }
 
 }  // namespace
 }  // namespace mxg
@@ -998,8 +998,7 @@ int mxg_filter_render(int kind, size_t V, size_t N, const double *d_in, const do
     MXG_REQUIRE(kind > MXG_FLT_BANDPASS || mod || d_coef,
                 "constant-parameter lores/hires/bandpass need d_coef from mxg_filter_coeffs_host");
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;  // the bank kernels are compiled for <= 256 lanes per workgroup (512 VGPRs/lane budget)
+    const int block = voice_block(V);
     hipStream_t st = resolve_stream(stream);
     double sr = (double)settings().sampleRate;
     if (!mod && (kind == MXG_FLT_LORES || kind == MXG_FLT_HIRES) && scan_applies(V, N))  // tolerance mode (scan.hip)
@@ -1016,10 +1015,10 @@ int mxg_filter_render(int kind, size_t V, size_t N, const double *d_in, const do
         if (rw >= 2 && pairs_ok) {
             KernelTimer kt("filter_kernel", st);
 #define MXG_FLP2(K, S)                                                                                                              \
-    if (chunk == 4) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 4>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
-    else if (chunk == 32) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 32>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
-    else if (chunk == 16) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 16>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
-    else hipLaunchKernelGGL((filter_pairs_kernel<K, S, 8>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out);
+    if (chunk == 4) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 4>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
+    else if (chunk == 32) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 32>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
+    else if (chunk == 16) hipLaunchKernelGGL((filter_pairs_kernel<K, S, 16>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out); \
+    else hipLaunchKernelGGL((filter_pairs_kernel<K, S, 8>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_cutoff, d_coef, d_st, d_out);
 #define MXG_FLP(K)                     \
     if (rw == 2) { MXG_FLP2(K, 0) }    \
     else if (rw == 3) { MXG_FLP2(K, 2) } \
@@ -1040,10 +1039,10 @@ int mxg_filter_render(int kind, size_t V, size_t N, const double *d_in, const do
     }
 #define MXG_FLT_LAUNCH(K)                                                                        \
     if (mod)                                                                                     \
-        hipLaunchKernelGGL((filter_kernel<K, true>), grid_for(V, block), dim3(block), 0, st, V, N, \
+        hipLaunchKernelGGL((filter_kernel<K, true>), voice_grid(V, block), dim3(block), 0, st, V, N, \
                            d_in, d_cutoff, cps, d_res, rps, d_coef, d_st, d_out, sr);            \
     else                                                                                         \
-        hipLaunchKernelGGL((filter_kernel<K, false>), grid_for(V, block), dim3(block), 0, st, V, N, \
+        hipLaunchKernelGGL((filter_kernel<K, false>), voice_grid(V, block), dim3(block), 0, st, V, N, \
                            d_in, d_cutoff, cps, d_res, rps, d_coef, d_st, d_out, sr);
     KernelTimer kt("filter_kernel", st);
     switch (kind) {
@@ -1067,9 +1066,9 @@ int mxg_filter_render_coefs(int kind, size_t V, size_t N, const double *d_in, co
     KernelTimer kt("filter_coefps_kernel", st);
     const int block = 256;
     switch (kind) {
-        case 0: hipLaunchKernelGGL((filter_coefps_kernel<0>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
-        case 1: hipLaunchKernelGGL((filter_coefps_kernel<1>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
-        default: hipLaunchKernelGGL((filter_coefps_kernel<2>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
+        case 0: hipLaunchKernelGGL((filter_coefps_kernel<0>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
+        case 1: hipLaunchKernelGGL((filter_coefps_kernel<1>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
+        default: hipLaunchKernelGGL((filter_coefps_kernel<2>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_coef_ps, d_st, d_out); break;
     }
     return check_hip(hipGetLastError(), "filter_coefps_kernel launch");
 }
@@ -1110,8 +1109,7 @@ int mxg_env_render(int mode, size_t V, size_t N, const double *d_in, const int32
     MXG_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (adsr) or 1 (ar)");
     MXG_REQUIRE(d_trig && d_par && d_holdtime && d_dst && d_ist && d_out, "null device pointer");
     if (V == 0 || N == 0) return MXG_OK;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;  // the bank kernels are compiled for <= 256 lanes per workgroup (512 VGPRs/lane budget)
+    const int block = voice_block(V);
     hipStream_t st = resolve_stream(stream);
     // 16-byte pair-row streams (knob rw_store, as mxg_filter_render: 0 automatic = write-through stores for blocks from 64 MB, 1 off,
     // 2 / 3 / 4 plain / write-through / non-temporal stores)
@@ -1120,7 +1118,7 @@ int mxg_env_render(int mode, size_t V, size_t N, const double *d_in, const int32
     if (rw == 0) rw = (V * N * sizeof(double) >= ((size_t)64 << 20)) ? 3 : 1;
     const int px = (rw >= 2 && pairs_ok) ? rw - 1 : 0;
 #define MXG_ENV_LAUNCH(M, I, P, X)                                                                      \
-    hipLaunchKernelGGL((env_kernel<M, I, P, X>), grid_for(V, block), dim3(block), 0, st, V, N, d_in, d_trig, \
+    hipLaunchKernelGGL((env_kernel<M, I, P, X>), voice_grid(V, block), dim3(block), 0, st, V, N, d_in, d_trig, \
                        tpv, d_par, d_holdtime, d_dst, d_ist, d_out)
 #define MXG_ENV_LAUNCH1(M, I, P)                        \
     switch (px) {                                       \
@@ -1165,8 +1163,7 @@ static int voice_launch(int mode, size_t V, size_t N, const double *d_freq, cons
                         double *d_ost, double *d_fst, double *d_dst, int64_t *d_ist, double *d_out, const double *d_pan, double *d_rows,
                         hipStream_t st) {
     const bool mix = d_rows != nullptr;
-    int block = tune_get("voice_block");
-    if (block > 256) block = 256;  // the bank kernels are compiled for <= 256 lanes per workgroup (512 VGPRs/lane budget)
+    int block = voice_block(V);
     // the store stream, as K1's (osc.hip, profiles/r03_osc_store.md): knob voice_store 0 = automatic (pair rows of write-through
     // 16-byte stores wherever whole pairs exist; XCD-contiguous numbering from 262 144 voices), 1 / 2 plain / nt 8-byte stores
     // (0 with voice_nt set: the round-2 rule), 3 / 4 / 5 pair rows plain / sc1 / nt
@@ -1199,7 +1196,7 @@ static int voice_launch(int mode, size_t V, size_t N, const double *d_freq, cons
         if (!d_out) store = 5;  // no per-voice block
         block = 512;            // 256 voices per workgroup: four producer + four consumer wavefronts
     }
-    const dim3 grid = mix ? grid_for(V, 256) : grid_for(V, block);
+    const dim3 grid = mix ? voice_grid(V, 256) : voice_grid(V, block);
     double sr = (double)settings().sampleRate;
 #define MXG_VOICE_LAUNCH(M, S, X, P, MX, D)                                                            \
     hipLaunchKernelGGL((voice_kernel<M, S, X, P, MX, D>), grid, dim3(block), 0, st, V, N, d_freq, \

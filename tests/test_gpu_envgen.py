@@ -110,3 +110,28 @@ def test_envgen_uploaded_state_parked_on_the_end_test(mx, port, loop):
     assert_bits_equal(o, e, "uploaded state")
     assert np.array_equal(bank.istate.numpy(), i)
     assert_bits_equal(bank.dstate.numpy(), d)
+
+
+@pytest.mark.parametrize("rw", [1, 2])
+@pytest.mark.parametrize("N", [1, 7, 9])
+@pytest.mark.parametrize("V", [2, 66])
+def test_envgen_blocks_shorter_than_a_chunk(mx, port, V, N, rw):
+    """Per-voice triggers in blocks of fewer rows than one chunk of 8 (and one row more), with the 8-byte stores (rw_store 1) and
+    with pair rows forced (2): the clamp of the prologue load is all that keeps the kernel inside the trigger block.  Two
+    consecutive blocks carry the state; stages of 2 .. 4 samples and triggers that change sign every few samples keep the state
+    machine moving inside them.  V = 2 is one pair under 62 shadow lanes, V = 66 a second wavefront of one pair."""
+    lv, tm, cv = [0, 1, 0.4, 0.4, 0], [0.05, 0.07, H, 0.1], [1, 1, 1, 1]   # 2, 3, hold, 4 samples at 44.1 kHz
+    trig = np.random.default_rng(1000 * V + 10 * N + rw).integers(-1, 2, (2 * N, V)).astype(np.float64)
+    L = mx.lib()
+    prev = L.mxg_tune(b"rw_store", rw)
+    try:
+        bank = mx.maxiEnvGenBank(V)
+        assert bank.setup(lv, tm, cv, False, True)
+        o = np.concatenate([bank.play(trig[:N]).numpy(), bank.play(trig[N:]).numpy()])
+    finally:
+        L.mxg_tune(b"rw_store", prev)
+    e1, d, i, _ = port.envgen(trig[:N], lv, tm, cv, 0, 1)
+    e2, d, i, _ = port.envgen(trig[N:], lv, tm, cv, 0, 1, dst=d, ist=i)
+    assert_bits_equal(o, np.concatenate([e1, e2]), "V %d N %d rw_store %d" % (V, N, rw))
+    assert np.array_equal(bank.istate.numpy(), i)
+    assert_bits_equal(bank.dstate.numpy(), d)
