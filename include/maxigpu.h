@@ -472,6 +472,13 @@ int mxg_rms_render(size_t V, size_t N, const double *d_in, const uint32_t *d_win
  * maxiDynamics::setAttackHigh / setReleaseHigh / setAttackLow / setReleaseLow are setupASR(10, 10) once, then
  * setTime(0, ms) / setTime(2, ms).  Host arithmetic only: bit-exact. */
 int mxg_envgen_set_time_host(double *h_stages, size_t nstages, size_t index, double ms);
+/* maxiEnvGen::setLevel(index, value) (H:2422-2437) and setCurve(index, value) (H:2440-2446) on a HOST [nstages][6] table.
+ * setLevel writes startlevel of row `index` and endlevel of row `index - 1`; index == nstages writes the last row's endlevel
+ * only; beyond that it returns 1 (the reference's `error`), else 0.  setCurve writes the curve of row `index` and returns 0
+ * always; for index >= nstages it writes nothing (the reference writes outside its vector for index == nstages).  A null table
+ * or nstages outside 1 .. 32: MXG_ERR_INVALID. */
+int mxg_envgen_set_level_host(double *h_stages, size_t nstages, size_t index, double value);
+int mxg_envgen_set_curve_host(double *h_stages, size_t nstages, size_t index, double value);
 
 /* ---- maxiSatReverb / maxiFreeVerb / maxiFreeVerbStereo (libs/maxiReverb.h, K13) ------------------------------------
  * A bank of V reverbs.  Every delay length is a constant of the class (samples, independent of the sample rate):
@@ -732,6 +739,30 @@ int mxg_line_prepare_host(size_t V, const double *h_start, const double *h_end, 
                           const int32_t *h_mask, double sample_rate, double *h_par, double *h_st);
 int mxg_line_render(size_t V, size_t N, const double *d_trig, double trig_const, const double *d_par, double *d_st, double *d_out,
                     void *stream);
+
+/* ---- maxiPolyBLEP: the anti-aliased oscillator (K20) --------------------------------------------------------------------
+ * V x maxiPolyBLEP::play(freq) (src/libs/maxiPolyBLEP.h over src/libs/PolyBLEP/PolyBLEP.cpp): per sample dt = freq / sample_rate,
+ * the waveform's sample on the phase t -- or a sine where (freq / sample_rate) * sample_rate >= sample_rate / 4 -- then
+ * t += dt; t -= (int64)t.  One waveform per launch, MXG_PBLEP_* in the reference's enum order.
+ * d_freq [V] (fps = 0) or [N][V] (fps = 1); d_pw [V] the pulse widths, NULL: 0.5; d_t [V] the phases, in/out; d_out [N][V],
+ * distinct from d_freq.  DOMAIN: finite frequencies with |freq / sample_rate| < 2^62, finite pulse widths, phases in (-1, 1)
+ * (what sync and play leave); a negative frequency is inside.
+ * The phase is BIT-EXACT.  TRIANGLE, SQUARE, RECTANGLE, SAWTOOTH, RAMP, MODIFIED_TRIANGLE, MODIFIED_SQUARE, TRIANGULAR_PULSE,
+ * TRAPEZOID_FIXED and TRAPEZOID_VARIABLE are BIT-EXACT wherever the sine fallback is not taken; SINE, COSINE and a fallback
+ * sample are within 1 ULP, the two rectified sines within 2^-50 absolute.
+ * Refused with MXG_ERR_INVALID: V == 0 or N == 0, a waveform outside 0 .. 13, sample_rate <= 0, a null d_freq / d_t / d_out.
+ * mxg_polyblep_host: the same arguments on HOST arrays, the same arithmetic on the CPU (no device needed). */
+enum {
+    MXG_PBLEP_SINE = 0, MXG_PBLEP_COSINE = 1, MXG_PBLEP_TRIANGLE = 2, MXG_PBLEP_SQUARE = 3, MXG_PBLEP_RECTANGLE = 4,
+    MXG_PBLEP_SAWTOOTH = 5, MXG_PBLEP_RAMP = 6, MXG_PBLEP_MODIFIED_TRIANGLE = 7, MXG_PBLEP_MODIFIED_SQUARE = 8,
+    MXG_PBLEP_HALF_WAVE_RECTIFIED_SINE = 9, MXG_PBLEP_FULL_WAVE_RECTIFIED_SINE = 10, MXG_PBLEP_TRIANGULAR_PULSE = 11,
+    MXG_PBLEP_TRAPEZOID_FIXED = 12, MXG_PBLEP_TRAPEZOID_VARIABLE = 13
+};
+#define MXG_PBLEP_WAVEFORMS 14
+int mxg_polyblep_render(int waveform, size_t V, size_t N, const double *d_freq, int fps, const double *d_pw, double sample_rate,
+                        double *d_t, double *d_out, void *stream);
+int mxg_polyblep_host(int waveform, size_t V, size_t N, const double *h_freq, int fps, const double *h_pw, double sample_rate,
+                      double *h_t, double *h_out);
 
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {

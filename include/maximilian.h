@@ -912,6 +912,38 @@ struct OscPool : Pool {  // state: phase, output (H:173,176)
     }
 };
 
+struct PolyBLEPPool : Pool {  // maxiPolyBLEP (include/maxiPolyBLEP.h): state = the phase t; method = the waveform (MXG_PBLEP_*)
+    PolyBLEPPool() : Pool(1, 0) {}
+    // a[0] the frequency, a[1] the pulse width, a[2] the sample rate -- one per launch: the call's key is its bits
+    static const void *rate_key(double sr) {
+        uintptr_t k = 0;
+        std::memcpy(&k, &sr, sizeof(k) < sizeof(sr) ? sizeof(k) : sizeof(sr));
+        return reinterpret_cast<const void *>(k);
+    }
+    unsigned derivable(int) const override { return 1u; }  // the frequency
+    void enqueue(Group &G) override {
+        const size_t n = G.m.size();
+        const int wf = G.sig[0].method;
+        const double sr = G.sig[0].a[2];
+        std::vector<double> hp(2 * n);
+        for (size_t j = 0; j < n; j++)
+            for (int k = 0; k < 2; k++) hp[(size_t)k * n + j] = G.sig[j].a[k];
+        double *dp = G.d_par.need(2 * n);
+        stage_begin(G, sizeof(double) * 2 * n + sizeof(double) * G.L * n + 64);
+        put(G, dp, hp.data(), sizeof(double) * 2 * n, "h2d polyblep");
+        if (G.varies(0)) {  // a derived frequency: one value per sample, [L][n]
+            std::vector<double> hf(G.L * n);
+            for (size_t t = 0; t < G.L; t++)
+                for (size_t j = 0; j < n; j++) hf[t * n + j] = G.arg(j, 0, t);
+            double *df = G.d_in.need(G.L * n);
+            put(G, df, hf.data(), sizeof(double) * hf.size(), "h2d polyblep freq");
+            check(mxg_polyblep_render(wf, n, G.L, df, 1, dp + n, sr, G.d_state.p, G.d_out.p, stream), "mxg_polyblep_render");
+            return;
+        }
+        check(mxg_polyblep_render(wf, n, G.L, dp, 0, dp + n, sr, G.d_state.p, G.d_out.p, stream), "mxg_polyblep_render");
+    }
+};
+
 struct EnvPool : Pool {  // state: amplitude, output | holdcount, attack/decay/sustain/hold/release phase (H:888-932)
     EnvPool() : Pool(2, 6) {}
     unsigned derivable(int) const override { return 1u; }  // the input signal
@@ -2804,12 +2836,31 @@ public:
         }
         MAXIGPU_CATCH(return true)
     }
+    // H:2422-2437 / H:2440-2446: host edits of the [nstages][6] stage table (mxg_envgen_set_level_host / _set_curve_host), like
+    // setTime.  setLevel returns the reference's `error` (an index past the number of stages), setCurve 0 always; with no stages
+    // both do nothing.
+    bool setLevel(size_t index, double value) { return edit_stage(mxg_envgen_set_level_host, index, value, index > stage_count()); }
+    bool setCurve(size_t index, double value) { return edit_stage(mxg_envgen_set_curve_host, index, value, false); }
     void setRetrigger(const bool val) { pool().settle(slot_); shape_.retrigger = val; }
     bool getRetrigger() { return shape_.retrigger; }
     void setLoop(const bool val) { pool().settle(slot_); shape_.loop = val; }
     bool getLoop() { return shape_.loop; }
 
 private:
+    size_t stage_count() const { return shape_.d_stages && shape_.nstages > 0 ? static_cast<size_t>(shape_.nstages) : 0; }
+    bool edit_stage(int (*edit)(double *, size_t, size_t, double), size_t index, double value, bool error) {
+        MAXIGPU_TRY {
+        const size_t ns = stage_count();
+        if (error || ns == 0 || index > ns) return error;
+        pool().settle(slot_);
+        std::vector<double> tab(6 * ns);
+        if (!maxigpu::ps::check(mxg_memcpy_d2h(tab.data(), shape_.d_stages, sizeof(double) * tab.size(), nullptr), "d2h stages")) return error;
+        if (edit(tab.data(), ns, index, value) < 0) return error;
+        maxigpu::ps::check(mxg_memcpy_h2d(shape_.d_stages, tab.data(), sizeof(double) * tab.size(), nullptr), "h2d stages");
+        return error;
+        }
+        MAXIGPU_CATCH(return error)
+    }
     void copy_from(const maxiEnvGen &o) {  // its own copy of the stage table on the device, the same running state
         MAXIGPU_TRY {
         pool().settle(const_cast<maxiEnvGen &>(o).slot_);

@@ -19,6 +19,7 @@
 // mxg_last_error(); nothing here falls back to the CPU.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -1082,6 +1083,53 @@ private:
     size_t V;
     std::vector<double> par_, st_;
     maxigpu::DeviceArray<double> d_par_, d_st_;
+};
+
+// V x maxiPolyBLEP (mxg_polyblep_render, K20): one waveform for the bank, a pulse width and a phase per voice, the phase carried
+// from call to call.  set_waveform / set_pulse_width / sync act between two blocks, as the reference's setters do between two
+// samples.  render(N, d_freq, per_sample, ...) reads one frequency per voice [V] or a block [N][V].
+class maxiPolyBLEPBank {
+public:
+    explicit maxiPolyBLEPBank(size_t voices, double sampleRate = (double)maxiSettings::sampleRate) : V(voices), sr_(sampleRate) {
+        d_t_.upload(std::vector<double>(V, 0.0));  // the reference's constructor: SINE, pulse width 0.5, t = 0
+    }
+    size_t voices() const { return V; }
+    void set_waveform(int waveform) {
+        if (waveform < 0 || waveform >= MXG_PBLEP_WAVEFORMS) throw std::runtime_error("maxiPolyBLEPBank::set_waveform: one of MXG_PBLEP_*");
+        wf_ = waveform;
+    }
+    int waveform() const { return wf_; }
+    void set_sample_rate(double sampleRate) { sr_ = sampleRate; }
+    void set_pulse_width(const std::vector<double> &pw) {
+        if (pw.size() != V) throw std::runtime_error("maxiPolyBLEPBank::set_pulse_width: one value per voice");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_pw_.upload(pw);
+        has_pw_ = true;
+    }
+    void set_pulse_width(double pw) { set_pulse_width(std::vector<double>(V, pw)); }
+    // PolyBLEP::sync: t = phase - (int64)phase, a negative phase t = phase + (1 - (int64)phase)
+    static double wrap(double phase) { return phase >= 0 ? phase - std::trunc(phase) : phase + (1 - std::trunc(phase)); }
+    void sync(const std::vector<double> &phases) {
+        if (phases.size() != V) throw std::runtime_error("maxiPolyBLEPBank::sync: one value per voice");
+        std::vector<double> t(V);
+        for (size_t v = 0; v < V; v++) t[v] = wrap(phases[v]);
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_t_.upload(t);
+    }
+    void sync(double phase) { sync(std::vector<double>(V, phase)); }
+    void render(size_t N, const double *d_freq, bool per_sample, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_polyblep_render(wf_, V, N, d_freq, per_sample ? 1 : 0, has_pw_ ? d_pw_.get() : nullptr, sr_, d_t_.get(), d_out, stream),
+                       "mxg_polyblep_render");
+    }
+    // the phases on the device [V]
+    double *phases() { return d_t_.get(); }
+
+private:
+    size_t V;
+    double sr_;
+    int wf_ = MXG_PBLEP_SINE;
+    bool has_pw_ = false;
+    maxigpu::DeviceArray<double> d_t_, d_pw_;
 };
 
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------

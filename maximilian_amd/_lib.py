@@ -107,6 +107,8 @@ SIGNATURES = {
     "mxg_rms_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
     "mxg_envgen_set_time_host": (c_int, [c_void_p, c_size_t, c_size_t, c_double]),
+    "mxg_envgen_set_level_host": (c_int, [c_void_p, c_size_t, c_size_t, c_double]),
+    "mxg_envgen_set_curve_host": (c_int, [c_void_p, c_size_t, c_size_t, c_double]),
     "mxg_reverb_layout_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_reverb_render": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -128,6 +130,8 @@ SIGNATURES = {
     "mxg_select_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mxg_line_prepare_host": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "mxg_line_render": (c_int, [c_size_t, c_size_t, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_polyblep_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "mxg_polyblep_host": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

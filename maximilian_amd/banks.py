@@ -1381,6 +1381,72 @@ class maxiLineBank(_Bank):
         return out
 
 
+POLYBLEP_WAVEFORMS = {"SINE": 0, "COSINE": 1, "TRIANGLE": 2, "SQUARE": 3, "RECTANGLE": 4, "SAWTOOTH": 5, "RAMP": 6, "MODIFIED_TRIANGLE": 7,
+                      "MODIFIED_SQUARE": 8, "HALF_WAVE_RECTIFIED_SINE": 9, "FULL_WAVE_RECTIFIED_SINE": 10, "TRIANGULAR_PULSE": 11,
+                      "TRAPEZOID_FIXED": 12, "TRAPEZOID_VARIABLE": 13}
+
+
+def polyblep_sync(phase):
+    """PolyBLEP::sync's wrap (P:101-108) on the host: t - (int64)t, a negative phase t + (1 - (int64)t)."""
+    t = np.asarray(phase, np.float64)
+    return np.where(t >= 0, t - np.trunc(t), t + (1 - np.trunc(t)))
+
+
+class maxiPolyBLEPBank(_Bank):
+    """V x maxiPolyBLEP (src/libs/maxiPolyBLEP.h; mxg_polyblep_render, K20): one waveform for the bank, a pulse width and a
+    phase per voice, the phase carried from call to call.  The phase and the ten arithmetic waveforms are the reference's
+    bits; the sine waveforms and the sine fallback at freq >= sampleRate / 4 are within the bounds of DESIGN.md section 4."""
+
+    def __init__(self, voices, sampleRate=None, stream=None):
+        super().__init__(voices, stream)
+        self.sampleRate = float(maxiSettings.sampleRate if sampleRate is None else sampleRate)
+        self.waveform = 0                     # the reference's constructor: SINE, pulse width 0.5, t = 0
+        self.pw = None                        # None: 0.5 on every voice
+        self.t = DeviceBuffer(self.V)
+
+    def set_waveform(self, waveform):
+        wf = POLYBLEP_WAVEFORMS[waveform] if isinstance(waveform, str) else int(waveform)
+        if not 0 <= wf < len(POLYBLEP_WAVEFORMS):
+            raise ValueError("waveform: one of POLYBLEP_WAVEFORMS")
+        self.waveform = wf
+
+    def set_pulse_width(self, pw):
+        """Per voice: scalar or [V]."""
+        self.pw = _as_dev(pw, self.V)
+
+    def set_sample_rate(self, sampleRate):
+        self.sampleRate = float(sampleRate)
+
+    def sync(self, phases=None, voices=None):
+        """maxiPolyBLEP::sync(phase) on every voice, or on `voices` (indices); phases scalar or one per synced voice.  Without an
+        argument: wait for the stream, as every bank does."""
+        if phases is None:
+            return super().sync()
+        if voices is None:
+            self.t.upload(np.ascontiguousarray(np.broadcast_to(polyblep_sync(phases), (self.V,))))
+            return
+        t = self.t.numpy()
+        t[np.atleast_1d(np.asarray(voices, np.int64))] = polyblep_sync(phases)
+        self.t.upload(t)
+
+    def render(self, freq, N=None, out=None, per_sample=False):
+        """freq: scalar / [V] with N, or per_sample a host or device [N][V] block."""
+        if per_sample:
+            f = freq if (isinstance(freq, DeviceBuffer) or hasattr(freq, "data_ptr")) else \
+                DeviceBuffer.from_numpy(np.ascontiguousarray(freq, np.float64))
+            N = f.shape[0]
+            _fx_dev(f, np.float64, "freq", (N * self.V,))
+        else:
+            if N is None:
+                raise ValueError("N: block-constant frequencies need the number of samples")
+            f = _as_dev(freq, self.V)
+        out = self._out(int(N), out)
+        check(lib().mxg_polyblep_render(self.waveform, self.V, int(N), _ptr(f), 1 if per_sample else 0, _ptr(self.pw), self.sampleRate,
+                                        self.t.ptr, _ptr(out), self.stream), "mxg_polyblep_render")
+        self._keep = f  # keep the parameter buffer alive until the next call
+        return out
+
+
 KURAMOTO_WANT = {"mix": 1, "phases": 2}
 KURAMOTO_MAX_N = 64
 

@@ -98,4 +98,25 @@ int mxg_envgen_set_time_host(double *h_stages, size_t nstages, size_t index, dou
     return dyn_envgen_set_time(h_stages, nstages, index, ms, (double)settings().sampleRate);
 }
 
+// maxiEnvGen::setLevel (H:2422-2437) / setCurve (H:2440-2446) on a host [nstages][6] table (include/maxigpu.h)
+int mxg_envgen_set_level_host(double *h_stages, size_t nstages, size_t index, double value) {
+    MXG_REQUIRE(h_stages, "null pointer");
+    MXG_REQUIRE(nstages >= 1 && nstages <= (size_t)kDynMaxStages, "nstages out of [1, 32]");
+    if (index > nstages) return 1;
+    if (index == nstages) {
+        h_stages[6 * (index - 1) + 1] = value;
+    } else {
+        h_stages[6 * index] = value;
+        if (index > 0) h_stages[6 * (index - 1) + 1] = value;
+    }
+    return 0;
+}
+
+int mxg_envgen_set_curve_host(double *h_stages, size_t nstages, size_t index, double value) {
+    MXG_REQUIRE(h_stages, "null pointer");
+    MXG_REQUIRE(nstages >= 1 && nstages <= (size_t)kDynMaxStages, "nstages out of [1, 32]");
+    if (index < nstages) h_stages[6 * index + 3] = value;
+    return 0;
+}
+
 }  // extern "C"

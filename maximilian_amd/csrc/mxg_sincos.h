@@ -33,6 +33,11 @@
 #define __forceinline__ inline
 #define MXG_TWOPI 6.283185307179586476925286766559
 #endif
+#if defined(__HIPCC__)
+#define MXG_SINCOS_HD __host__ __device__ __forceinline__
+#else
+#define MXG_SINCOS_HD inline
+#endif
 
 namespace mxg {
 
@@ -66,9 +71,9 @@ __device__ __forceinline__ double fma_kk(double a, double k1, double k0) {  // a
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(k1), "v"(k0));
     return d;
 }
-#else
-__device__ __forceinline__ double fma_k(double a, double b, double k) { return fma(a, b, k); }
-__device__ __forceinline__ double fma_kk(double a, double k1, double k0) { return fma(a, k1, k0); }
+#else  // the host pass: sincos_tab below also runs on the host (mxg_polyblep_host)
+MXG_SINCOS_HD double fma_k(double a, double b, double k) { return fma(a, b, k); }
+MXG_SINCOS_HD double fma_kk(double a, double k1, double k0) { return fma(a, k1, k0); }
 #endif
 
 // sin and cos of y + t on [-pi/4, pi/4] (t = tail of the reduced argument)
@@ -172,7 +177,7 @@ __device__ __forceinline__ SinTabK sintab_k() {
 // (entries 0 .. 1024: the period and its repetition): no range test, no sign to restore, no index wrap.
 #define MXG_SINTAB_WIDE_LEN (4 * 1025)
 template <bool COS, bool TRUST = false>
-MXG_NO_CONTRACT __device__ __forceinline__ double sincos_tab(double x, const double *tab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
+MXG_NO_CONTRACT MXG_SINCOS_HD double sincos_tab(double x, const double *tab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
     if constexpr (!TRUST)
         if (!(fabs(x) <= 64.0)) return COS ? cos(x) : sin(x);
     const double ax = TRUST ? x : fabs(x);
