@@ -245,3 +245,259 @@ private:
         else par_[row * kMax + currentVoice] = value;
     }
 };
+
+// ---- maxiKick / maxiSnare / maxiHats (src/libs/maxiSynths.h:20-120, maxiSynths.cpp:11-259) --------------------------------------
+// DROP-INS for the three drum voices: value types with the reference's public surface, whose play() is ONE launch of the fused drum
+// kernel (mxg_drum_render, K21) on a bank of one voice, in the manner of maxiFlanger / maxiDynamics.  What takes effect, read at every
+// play(): envelope.attack / decay / sustain / release (setAttack / setDecay / setSustain / setRelease), envelope.holdtime,
+// envelope.trigger (trigger() sets it to 1, play() puts a 1 back to 0), the hats' filter.setCutoff / setResonance, and every public
+// scalar (pitch, distortion, cutoff, resonance, gain, inverse, useDistortion, useFilter, useLimiter).  Snare and hats draw rand()
+// at the call, one draw per play() as maxiOsc::noise does.  Departures, all defined:
+//   * cutoff and resonance start at 0.0 where the reference leaves them uninitialised (maxiSnare filters by default): lores clamps
+//     them to 10 Hz and 1.
+//   * The voice's running state (oscillator phase, envelope state machine, filter state) lives with the drum on the device.  The
+//     public sub-objects tone, noise, envelope, distort and filter carry the PARAMETERS; their own running state does not alias the
+//     drum's (as maxiFlanger::dl).
+//   * The member `output` holds what play() returned (after the gain and the limiter), envOut the envelope's value of the call.
+#include "maxiClock.h"
+
+namespace maxigpu {
+namespace ps {
+template <int KIND>
+struct DrumLine {
+    // d_blk, doubles unless said.  Uploaded per call, @0..127: trig, pitch, attack, decay, sustain, release, shape, coef [5], gain, (out),
+    // holdtime int64, the draw int32.  Read back, @104..223: out, (holdtime, draw), then the state: phase, amplitude, output, int64
+    // holdcount + five phase flags, filter state [3].
+    static constexpr size_t kBlk = 28 * 8, kArgs = 16 * 8, kState = 16;
+    unsigned char *d_blk = nullptr;
+    bool init() {
+        if (dead()) return false;
+        if (d_blk) return true;
+        if (!check(mxg_init(-1), "mxg_init")) return false;
+        d_blk = static_cast<unsigned char *>(mxg_malloc(kBlk));
+        if (!d_blk) {
+            check(MXG_ERR_HIP, "mxg_malloc (drum voice)");
+            return false;
+        }
+        return check(mxg_memset(d_blk, 0, kBlk, nullptr), "mxg_memset") && check(mxg_sync(), "mxg_sync");
+    }
+    void release() {
+        if (d_blk) mxg_free(d_blk);
+        d_blk = nullptr;
+    }
+    void copy_from(const DrumLine &o) {
+        release();
+        if (!o.d_blk || !init()) return;
+        check(mxg_memcpy_d2d_async(d_blk, o.d_blk, kBlk, nullptr), "d2d drum state") && check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    // one play(); env_out receives envelope.output after the call
+    double run(int flags, bool trig, int32_t draw, double pitch, const double (&par)[4], long holdtime, double shape, const double (&coef)[5],
+               double gain, double &env_out) {
+        if (!init()) return 0.0;
+        double h[kArgs / 8] = {0};
+        h[0] = trig ? 1.0 : 0.0;
+        h[1] = pitch;
+        for (int i = 0; i < 4; i++) h[2 + i] = par[i];
+        h[6] = shape;
+        for (int i = 0; i < 5; i++) h[7 + i] = coef[i];
+        h[12] = gain;
+        const int64_t hold = holdtime;
+        std::memcpy(&h[14], &hold, 8);
+        std::memcpy(&h[15], &draw, 4);
+        if (!check(mxg_memcpy_h2d(d_blk, h, kArgs, nullptr), "h2d drum arguments")) return 0.0;
+        double *p = reinterpret_cast<double *>(d_blk);
+        const int st = mxg_drum_render(KIND, flags, 1, 1, p, 0, KIND == MXG_DRUM_KICK ? nullptr : reinterpret_cast<int32_t *>(p + 15), p + 1, p + 2,
+                                       reinterpret_cast<int64_t *>(p + 14), p + 6, p + 7, p + 12, p + kState, p + kState + 1,
+                                       reinterpret_cast<int64_t *>(p + kState + 3), p + kState + 9, p + 13, nullptr);
+        if (!check(st, "mxg_drum_render")) return 0.0;
+        double back[6] = {0};  // out, holdtime, draw, phase, amplitude, envelope.output
+        if (!check(mxg_memcpy_d2h(back, d_blk + 13 * 8, sizeof(back), nullptr), "d2h drum output")) return 0.0;
+        env_out = back[5];
+        return back[0];
+    }
+};
+}  // namespace ps
+}  // namespace maxigpu
+
+#define MAXIGPU_DRUM_COMMON(NAME, KIND)                                                                                                  \
+    maxigpu::ps::DrumLine<KIND> line_;                                                                                                   \
+    void copy_scalars(const NAME &o) {                                                                                                   \
+        pitch = o.pitch; output = o.output; outputD = o.outputD; envOut = o.envOut; useDistortion = o.useDistortion;                     \
+        useLimiter = o.useLimiter; useFilter = o.useFilter; distortion = o.distortion; inverse = o.inverse; cutoff = o.cutoff;           \
+        resonance = o.resonance; gain = o.gain;                                                                                          \
+    }                                                                                                                                    \
+    int flags_() const {                                                                                                                 \
+        return (inverse ? MXG_DRUM_INVERSE : 0) | (useDistortion ? MXG_DRUM_DISTORTION : 0) | (useFilter ? MXG_DRUM_FILTER : 0) |        \
+               (useLimiter ? MXG_DRUM_LIMITER : 0);                                                                                      \
+    }                                                                                                                                    \
+    double play_(int32_t draw, const double (&coef)[5]) {                                                                                \
+        const double par[4] = {envelope.attack, envelope.decay, envelope.sustain, envelope.release};                                     \
+        double e = 0.0;                                                                                                                  \
+        output = line_.run(flags_(), envelope.trigger == 1, draw, pitch, par, envelope.holdtime, distortion, coef, gain, e);             \
+        envOut = inverse ? fabs(1 - e) : e;                                                                                              \
+        if (envelope.trigger == 1) envelope.trigger = 0;                                                                                 \
+        return output;                                                                                                                   \
+    }                                                                                                                                    \
+    void lores_coef_(double (&coef)[5]) const {                                                                                          \
+        double c3[3] = {0, 0, 0};                                                                                                        \
+        if (useFilter) maxigpu::ps::check(mxg_filter_coeffs_host(MXG_FLT_LORES, 1, &cutoff, &resonance, c3), "mxg_filter_coeffs_host");  \
+        coef[0] = c3[0]; coef[1] = c3[1]; coef[2] = coef[3] = coef[4] = 0.0;                                                             \
+    }
+
+class maxiKick {
+public:
+    maxiKick() {  // maxiSynths.cpp:11-21
+        envelope.setAttack(0);
+        setPitch(200);
+        envelope.setDecay(1);
+        envelope.setSustain(1);
+        envelope.setRelease(500);
+        envelope.holdtime = 1;
+        envelope.trigger = 0;
+    }
+    maxiKick(const maxiKick &o) : kick(o.kick), envelope(o.envelope), distort(o.distort), filter(o.filter) { copy_scalars(o); line_.copy_from(o.line_); }
+    maxiKick &operator=(const maxiKick &o) {
+        if (this != &o) { kick = o.kick; envelope = o.envelope; distort = o.distort; filter = o.filter; copy_scalars(o); line_.copy_from(o.line_); }
+        return *this;
+    }
+    ~maxiKick() { line_.release(); }
+    double play() {  // maxiSynths.cpp:23-73
+        double coef[5];
+        lores_coef_(coef);
+        return play_(0, coef);
+    }
+    void trigger() { envelope.trigger = 1; }
+    void setRelease(double releaseD) { envelope.setRelease(releaseD); }
+    // the kick's members are private in the reference: these pairs are its whole parameter surface (the three switch getters
+    // return double there too)
+    void setPitch(double hz) { pitch = hz; }
+    void setDistortion(double shape) { distortion = shape; }
+    void setCutoff(double hz) { cutoff = hz; }
+    void setResonance(double q) { resonance = q; }
+    void setUseDistortion(bool on) { useDistortion = on; }
+    void setUseFilter(bool on) { useFilter = on; }
+    void setUseLimiter(bool on) { useLimiter = on; }
+    double getPitch() const { return pitch; }
+    double getDistortion() const { return distortion; }
+    double getCutoff() const { return cutoff; }
+    double getResonance() const { return resonance; }
+    double getUseDistortion() const { return useDistortion ? 1.0 : 0.0; }
+    double getUseFilter() const { return useFilter ? 1.0 : 0.0; }
+    double getUseLimiter() const { return useLimiter ? 1.0 : 0.0; }
+
+private:
+    double pitch = 0;
+    double output = 0;
+    double outputD = 0;
+    double envOut = 0;
+    bool useDistortion = false;
+    bool useLimiter = false;
+    bool useFilter = false;
+    double distortion = 0;
+    bool inverse = false;
+    double cutoff = 0;
+    double resonance = 0;
+    double gain = 1;
+    maxiOsc kick;
+    maxiEnv envelope;
+    maxiDistortion distort;
+    maxiFilter filter;
+    MAXIGPU_DRUM_COMMON(maxiKick, MXG_DRUM_KICK)
+};
+
+class maxiSnare {
+public:
+    maxiSnare() {  // maxiSynths.cpp:93-103
+        envelope.setAttack(0);
+        setPitch(800);
+        envelope.setDecay(20);
+        envelope.setSustain(0.05);
+        envelope.setRelease(300);
+        envelope.holdtime = 1;
+        envelope.trigger = 0;
+    }
+    maxiSnare(const maxiSnare &o) : tone(o.tone), noise(o.noise), envelope(o.envelope), distort(o.distort), filter(o.filter) { copy_scalars(o); line_.copy_from(o.line_); }
+    maxiSnare &operator=(const maxiSnare &o) {
+        if (this != &o) { tone = o.tone; noise = o.noise; envelope = o.envelope; distort = o.distort; filter = o.filter; copy_scalars(o); line_.copy_from(o.line_); }
+        return *this;
+    }
+    ~maxiSnare() { line_.release(); }
+    double play() {  // maxiSynths.cpp:105-156
+        double coef[5];
+        lores_coef_(coef);
+        return play_((int32_t)rand(), coef);
+    }
+    void setPitch(double newPitch) { pitch = newPitch; }
+    void setRelease(double releaseD) { envelope.setRelease(releaseD); }
+    void trigger() { envelope.trigger = 1; }
+    double pitch = 0;
+    double output = 0;
+    double outputD = 0;
+    double envOut = 0;
+    bool useDistortion = false;
+    bool useLimiter = false;
+    bool useFilter = true;
+    double distortion = 0;
+    bool inverse = false;
+    double cutoff = 0;
+    double resonance = 0;
+    double gain = 1;
+    maxiOsc tone;
+    maxiOsc noise;
+    maxiEnv envelope;
+    maxiDistortion distort;
+    maxiFilter filter;
+
+private:
+    MAXIGPU_DRUM_COMMON(maxiSnare, MXG_DRUM_SNARE)
+};
+
+class maxiHats {
+public:
+    maxiHats() {  // maxiSynths.cpp:176-188
+        envelope.setAttack(0);
+        setPitch(12000);
+        envelope.setDecay(20);
+        envelope.setSustain(0.1);
+        envelope.setRelease(300);
+        envelope.holdtime = 1;
+        envelope.trigger = 0;
+        filter.setCutoff(8000);
+        filter.setResonance(1);
+    }
+    maxiHats(const maxiHats &o) : tone(o.tone), noise(o.noise), envelope(o.envelope), distort(o.distort), filter(o.filter) { copy_scalars(o); line_.copy_from(o.line_); }
+    maxiHats &operator=(const maxiHats &o) {
+        if (this != &o) { tone = o.tone; noise = o.noise; envelope = o.envelope; distort = o.distort; filter = o.filter; copy_scalars(o); line_.copy_from(o.line_); }
+        return *this;
+    }
+    ~maxiHats() { line_.release(); }
+    double play() {  // maxiSynths.cpp:190-241: the SVF's coefficients are filter's (setCutoff / setResonance); cutoff / resonance are never read
+        double coef[5];
+        filter.coefficients(coef);
+        return play_((int32_t)rand(), coef);
+    }
+    void setPitch(double newPitch) { pitch = newPitch; }
+    void setRelease(double releaseD) { envelope.setRelease(releaseD); }
+    void trigger() { envelope.trigger = 1; }
+    double pitch = 0;
+    double output = 0;
+    double outputD = 0;
+    double envOut = 0;
+    bool useDistortion = false;
+    bool useLimiter = false;
+    bool useFilter = false;
+    double distortion = 0;
+    bool inverse = false;
+    double cutoff = 0;
+    double resonance = 0;
+    double gain = 1;
+    maxiOsc tone;
+    maxiOsc noise;
+    maxiEnv envelope;
+    maxiDistortion distort;
+    maxiSVF filter;
+
+private:
+    MAXIGPU_DRUM_COMMON(maxiHats, MXG_DRUM_HATS)
+};
+#undef MAXIGPU_DRUM_COMMON

@@ -764,6 +764,61 @@ int mxg_polyblep_render(int waveform, size_t V, size_t N, const double *d_freq, 
 int mxg_polyblep_host(int waveform, size_t V, size_t N, const double *h_freq, int fps, const double *h_pw, double sample_rate,
                       double *h_t, double *h_out);
 
+/* ---- maxiKick / maxiSnare / maxiHats and maxiClock: the fused drum voices (K21) ------------------------------------------
+ * V x play() of one drum class (src/libs/maxiSynths.cpp:11-259), N samples: envOut = envelope.adsr(1., trigger), optionally
+ * fabs(1 - envOut); the voice -- kick sinewave(pitch*envOut)*envOut, snare (triangle(pitch*(0.1+(envOut*0.85))) + noise())*envOut,
+ * hats (sinebuf(pitch) + noise())*envOut --; optionally fastAtanDist(output, distortion); optionally the filter (kick / snare
+ * lores(output, cutoff, resonance), hats maxiSVF::play(output, 0., 0., 1., 0.)); output*gain, optionally limited to exactly +-1.
+ * One kind per launch; flags = MXG_DRUM_INVERSE | DISTORTION | FILTER | LIMITER (the members inverse, useDistortion, useFilter,
+ * useLimiter), constant per call.  The sample rate is mxg_settings'.
+ *   d_trig   doubles [N][V] (tpv = 1) or [N] (tpv = 0), what mxg_seq_render's d_trig and mxg_clock_render's d_tick hold: a
+ *            non-zero entry means trigger() was called before that play().  NULL: never.
+ *   d_rand   int32 [N][V], as for mxg_osc_noise: the rand() draw voice v's noise() takes at sample n.  Required for snare and
+ *            hats; REFUSED (not ignored) for the kick, which draws nothing.
+ *   d_pitch [V]; d_env_par [4][V] attack, decay, sustain, release as the setters store them (mxg_env_coeff_host), d_holdtime int64
+ *            [V] (the constructors: attack 1 -- setAttack(0) --, holdtime 1); d_shape [V] the member distortion (NULL unless
+ *            DISTORTION); d_gain [V] (NULL: 1).
+ *   d_coef   kick / snare: [3][V] as mxg_filter_coeffs_host(MXG_FLT_LORES, ...) writes it (rows c, r are read); hats: [5][V] as
+ *            mxg_svf_coeffs_host writes it (the hats' filter.setCutoff / setResonance; the constructor: 8000, 1).  NULL only
+ *            without FILTER.
+ *   State, in / out, plain arrays; a fresh object is all zeros (mxg_memset):
+ *     d_phase [V]      kick.phase / tone.phase
+ *     d_dst   [2][V]   envelope.amplitude, envelope.output           } mxg_env_render's layout
+ *     d_ist   [6][V]   int64: holdcount, attackphase, decayphase, sustainphase, holdphase, releasephase
+ *     d_fst   [3][V]   kick / snare: filter.x, filter.y, (unused); hats: filter.v0z, v1, v2
+ *   d_out [N][V], distinct from d_trig and d_rand.
+ * DOMAIN: finite parameters; the hats' pitch in [0, sample rate) and its phase in [-1, 511), as maxiOsc::sinebuf's table read needs.
+ * Snare, hats and every state row but the kick's filter state are BIT-EXACT (host coefficients); the kick's output carries its
+ * sine's <= 1 ULP through the later stages.
+ * Refused with MXG_ERR_INVALID: V == 0 or N == 0, an unknown kind or flag, a missing required pointer, d_rand given for the kick,
+ * d_out overlapping d_trig or d_rand.
+ * mxg_drum_host: the same arguments on HOST arrays, the same arithmetic on the CPU (no device needed). */
+enum { MXG_DRUM_KICK = 0, MXG_DRUM_SNARE = 1, MXG_DRUM_HATS = 2 };
+#define MXG_DRUM_KINDS 3
+#define MXG_DRUM_INVERSE 1
+#define MXG_DRUM_DISTORTION 2
+#define MXG_DRUM_FILTER 4
+#define MXG_DRUM_LIMITER 8
+int mxg_drum_render(int kind, int flags, size_t V, size_t N, const double *d_trig, int tpv, const int32_t *d_rand,
+                    const double *d_pitch, const double *d_env_par, const int64_t *d_holdtime, const double *d_shape,
+                    const double *d_coef, const double *d_gain, double *d_phase, double *d_dst, int64_t *d_ist, double *d_fst,
+                    double *d_out, void *stream);
+int mxg_drum_host(int kind, int flags, size_t V, size_t N, const double *h_trig, int tpv, const int32_t *h_rand,
+                  const double *h_pitch, const double *h_env_par, const int64_t *h_holdtime, const double *h_shape,
+                  const double *h_coef, const double *h_gain, double *h_phase, double *h_dst, int64_t *h_ist, double *h_fst,
+                  double *h_out);
+/* V x maxiClock::ticker() (src/libs/maxiClock.cpp:16-28), N samples: currentCount = floor(timer.phasor(bps)); a sample ticks where
+ * lastCount != currentCount, and playHead counts the ticks.  ticker() never writes lastCount, so with lastCount 0 a tick is the one
+ * sample per wrap on which the phasor returns a phase >= 1.  d_bps [V] (setTempo: (bpm / 60.) * ticks); d_clk [V] timer.phase,
+ * in / out; d_lastcount int32 [V], read only (NULL: 0); d_playhead int64 [V], in / out; d_count int32 [V], out: currentCount after
+ * the block; d_tick [N][V] doubles 1.0 / 0.0, which feeds mxg_drum_render's d_trig directly.  Bit-exact.
+ * Refused with MXG_ERR_INVALID: V == 0 or N == 0, a null d_bps / d_clk / d_playhead / d_count / d_tick, d_tick overlapping any of
+ * the other arrays (all arrays are distinct). */
+int mxg_clock_render(size_t V, size_t N, const double *d_bps, double *d_clk, const int32_t *d_lastcount, int64_t *d_playhead,
+                     int32_t *d_count, double *d_tick, void *stream);
+int mxg_clock_host(size_t V, size_t N, const double *h_bps, double *h_clk, const int32_t *h_lastcount, int64_t *h_playhead,
+                   int32_t *h_count, double *h_tick);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

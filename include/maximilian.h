@@ -2691,6 +2691,8 @@ public:
     maxiSVF &operator=(const maxiSVF &o) { if (this != &o) copy_from(o); return *this; }
     void setCutoff(double cutoff) { setParams(cutoff, res); }
     void setResonance(double q) { setParams(freq, q); }
+    // g1, g2, g3, g4, k as setParams left them (maxiHats hands them to the fused drum voice: include/maxiSynths.h)
+    void coefficients(double (&c)[5]) const { for (int i = 0; i < 5; i++) c[i] = coef_[i]; }
     double play(double w, double lpmix, double bpmix, double hpmix, double notchmix) {
         maxigpu::ps::Call c;
         c.method = 1;

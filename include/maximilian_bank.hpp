@@ -1132,6 +1132,121 @@ private:
     maxigpu::DeviceArray<double> d_t_, d_pw_;
 };
 
+// V x maxiKick / maxiSnare / maxiHats (src/libs/maxiSynths.h; mxg_drum_render, K21): KIND is MXG_DRUM_KICK / SNARE / HATS.  The
+// setters take the reference's units (ms through mxg_env_coeff_host, cutoff / resonance through the coefficient hosts); the four
+// switches are one value for the bank.  State, carried from call to call, all zero in a fresh bank: phase [V], dst [2][V], ist
+// int64 [6][V] (mxg_env_render's layout), fst [3][V].  cutoff / resonance start at 0.0 where the reference leaves them
+// uninitialised (lores clamps them to 10 Hz and 1).  The hats' SVF takes setFilterCutoff / setFilterResonance (the reference's
+// filter.setCutoff / setResonance; the constructor: 8000, 1); their cutoff / resonance are, as in the reference, never read.
+template <int KIND>
+class maxiDrumBank {
+public:
+    bool inverse = false, useDistortion = false, useFilter = (KIND == MXG_DRUM_SNARE), useLimiter = false;
+
+    explicit maxiDrumBank(size_t voices)
+        : V(voices), pitch_(V, KIND == MXG_DRUM_KICK ? 200. : (KIND == MXG_DRUM_SNARE ? 800. : 12000.)), env_(4 * V), hold_(V, 1),
+          shape_(V, 0.), cutoff_(V, 0.), res_(V, 0.), gain_(V, 1.), svf_cutoff_(V, 8000.), svf_res_(V, 1.), d_phase_(V), d_dst_(2 * V),
+          d_ist_(6 * V), d_fst_(3 * V) {
+        setAttack(0);
+        setDecay(KIND == MXG_DRUM_KICK ? 1 : 20);
+        setSustain(KIND == MXG_DRUM_KICK ? 1 : (KIND == MXG_DRUM_SNARE ? 0.05 : 0.1));
+        setRelease(KIND == MXG_DRUM_KICK ? 500 : 300);
+    }
+    size_t voices() const { return V; }
+    void setAttack(double ms) { row(0, mxg_env_coeff_host(0, ms)); }  // (0: divides by zero inside pow, attack = 1)
+    void setDecay(double ms) { row(1, mxg_env_coeff_host(1, ms)); }
+    void setSustain(double level) { row(2, level); }
+    void setRelease(double ms) { row(3, mxg_env_coeff_host(2, ms)); }
+    void setHoldtime(long samples) { fill(hold_, (int64_t)samples); }
+    void setPitch(double v) { fill(pitch_, v); }
+    void setPitch(const std::vector<double> &v) { assign(pitch_, v); }
+    void setDistortion(double v) { fill(shape_, v); }
+    void setCutoff(double v) { fill(cutoff_, v); }
+    void setResonance(double v) { fill(res_, v); }
+    void setGain(double v) { fill(gain_, v); }
+    void setFilterCutoff(double v) { fill(svf_cutoff_, v); }
+    void setFilterResonance(double v) { fill(svf_res_, v); }
+    int flags() const {
+        return (inverse ? MXG_DRUM_INVERSE : 0) | (useDistortion ? MXG_DRUM_DISTORTION : 0) | (useFilter ? MXG_DRUM_FILTER : 0) |
+               (useLimiter ? MXG_DRUM_LIMITER : 0);
+    }
+    // N x play() per voice.  d_trig: doubles [N][V] (per_voice) or [N], non-zero = trigger() before that play(), null = never (a
+    // maxiClockBank's tick block fits); d_rand: int32 [N][V], the rand() draws of snare and hats (null for the kick).
+    void render(size_t N, const double *d_trig, bool per_voice, const int32_t *d_rand, double *d_out, void *stream = nullptr) {
+        if (dirty_) {
+            std::vector<double> coef((KIND == MXG_DRUM_HATS ? 5 : 3) * V);
+            if (KIND == MXG_DRUM_HATS) maxigpu::check(mxg_svf_coeffs_host(V, svf_cutoff_.data(), svf_res_.data(), coef.data()), "mxg_svf_coeffs_host");
+            else maxigpu::check(mxg_filter_coeffs_host(MXG_FLT_LORES, V, cutoff_.data(), res_.data(), coef.data()), "mxg_filter_coeffs_host");
+            maxigpu::check(mxg_sync(), "mxg_sync");
+            d_pitch_.upload(pitch_); d_env_.upload(env_); d_hold_.upload(hold_); d_shape_.upload(shape_); d_coef_.upload(coef); d_gain_.upload(gain_);
+            dirty_ = false;
+        }
+        maxigpu::check(mxg_drum_render(KIND, flags(), V, N, d_trig, per_voice ? 1 : 0, d_rand, d_pitch_.get(), d_env_.get(), d_hold_.get(),
+                                       d_shape_.get(), d_coef_.get(), d_gain_.get(), d_phase_.get(), d_dst_.get(), d_ist_.get(), d_fst_.get(),
+                                       d_out, stream), "mxg_drum_render");
+    }
+    // the state on the device (get / set with DeviceArray::download / upload, i.e. mxg_memcpy_*)
+    maxigpu::DeviceArray<double> &phase() { return d_phase_; }
+    maxigpu::DeviceArray<double> &dstate() { return d_dst_; }
+    maxigpu::DeviceArray<int64_t> &istate() { return d_ist_; }
+    maxigpu::DeviceArray<double> &fstate() { return d_fst_; }
+
+private:
+    template <typename T>
+    void fill(std::vector<T> &a, T v) { std::fill(a.begin(), a.end(), v); dirty_ = true; }
+    void assign(std::vector<double> &a, const std::vector<double> &v) {
+        if (v.size() != V) throw std::runtime_error("maxiDrumBank: one value per voice");
+        a = v;
+        dirty_ = true;
+    }
+    void row(int r, double v) { std::fill(env_.begin() + r * V, env_.begin() + (r + 1) * V, v); dirty_ = true; }
+    size_t V;
+    bool dirty_ = true;
+    std::vector<double> pitch_, env_;
+    std::vector<int64_t> hold_;
+    std::vector<double> shape_, cutoff_, res_, gain_, svf_cutoff_, svf_res_;
+    maxigpu::DeviceArray<double> d_phase_, d_dst_;
+    maxigpu::DeviceArray<int64_t> d_ist_;
+    maxigpu::DeviceArray<double> d_fst_, d_pitch_, d_env_, d_shape_, d_coef_, d_gain_;
+    maxigpu::DeviceArray<int64_t> d_hold_;
+};
+using maxiKickBank = maxiDrumBank<MXG_DRUM_KICK>;
+using maxiSnareBank = maxiDrumBank<MXG_DRUM_SNARE>;
+using maxiHatsBank = maxiDrumBank<MXG_DRUM_HATS>;
+
+// V x maxiClock (src/libs/maxiClock.h; mxg_clock_render): render(N, d_tick) is N x ticker() per voice and writes the tick block
+// [N][V] of 1.0 / 0.0, which a drum bank's render takes as d_trig.  lastCount is only read, as in the reference.
+class maxiClockBank {
+public:
+    explicit maxiClockBank(size_t voices)
+        : V(voices), bpm_(V, 120.), ticks_(V, 1), d_clk_(V), d_playhead_(V), d_last_(V), d_count_(V) { setTempo(120.); }
+    size_t voices() const { return V; }
+    void setTempo(double bpm) { std::fill(bpm_.begin(), bpm_.end(), bpm); push(); }
+    void setTicksPerBeat(int ticksPerBeat) { std::fill(ticks_.begin(), ticks_.end(), ticksPerBeat); push(); }
+    void setLastCount(int n) { maxigpu::check(mxg_sync(), "mxg_sync"); d_last_.upload(std::vector<int32_t>(V, n)); }
+    void render(size_t N, double *d_tick, void *stream = nullptr) {
+        maxigpu::check(mxg_clock_render(V, N, d_bps_.get(), d_clk_.get(), d_last_.get(), d_playhead_.get(), d_count_.get(), d_tick, stream),
+                       "mxg_clock_render");
+    }
+    std::vector<int64_t> playHead() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_playhead_.download(); }
+    std::vector<int32_t> currentCount() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_count_.download(); }
+    maxigpu::DeviceArray<double> &phase() { return d_clk_; }
+
+private:
+    void push() {
+        std::vector<double> bps(V);
+        for (size_t v = 0; v < V; v++) bps[v] = (bpm_[v] / 60.) * ticks_[v];  // setTempo: bps = (bpm/60.)*ticks
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_bps_.upload(bps);
+    }
+    size_t V;
+    std::vector<double> bpm_;
+    std::vector<int> ticks_;
+    maxigpu::DeviceArray<double> d_clk_, d_bps_;
+    maxigpu::DeviceArray<int64_t> d_playhead_;
+    maxigpu::DeviceArray<int32_t> d_last_, d_count_;
+};
+
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
 namespace maxigpu {
 // lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device

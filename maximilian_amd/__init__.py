@@ -14,6 +14,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiZXToPulseBank, seq_table, seq_ratio_tables, maxiAnalysisBank, maxiKuramotoBank, envfollow_coeff, analysis_want, OSC_WAVEFORMS,
                     maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
                     maxiPolyBLEPBank, polyblep_sync, POLYBLEP_WAVEFORMS,
+                    maxiKickBank, maxiSnareBank, maxiHatsBank, maxiClockBank, DRUM_KINDS,
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import (maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
                        padded_stream)

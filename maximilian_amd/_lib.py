@@ -132,6 +132,10 @@ SIGNATURES = {
     "mxg_line_render": (c_int, [c_size_t, c_size_t, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_polyblep_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "mxg_polyblep_host": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
+    "mxg_drum_render": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_int] + [c_void_p] * 13),
+    "mxg_drum_host": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_int] + [c_void_p] * 12),
+    "mxg_clock_render": (c_int, [c_size_t, c_size_t] + [c_void_p] * 7),
+    "mxg_clock_host": (c_int, [c_size_t, c_size_t] + [c_void_p] * 6),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

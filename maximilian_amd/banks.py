@@ -1880,3 +1880,155 @@ class maxiSampleBank(_Bank):
             self.clear()
         except Exception:
             pass
+
+
+DRUM_KINDS = {"kick": 0, "snare": 1, "hats": 2}
+DRUM_INVERSE, DRUM_DISTORTION, DRUM_FILTER, DRUM_LIMITER = 1, 2, 4, 8
+
+
+class _DrumBank(_Bank):
+    """V x one drum class of src/libs/maxiSynths.h (mxg_drum_render, K21).  The setters take the reference's units; the members
+    inverse / useDistortion / useFilter / useLimiter are one value for the bank (constant per launch).  State, carried from call to
+    call (DeviceBuffers: numpy() / upload() go through mxg_memcpy_*): phase [V], dstate [2][V] and istate int64 [6][V] as
+    maxiEnvBank's, fstate [3][V] (lores x, y | SVF v0z, v1, v2).  cutoff / resonance start at 0.0 where the reference leaves them
+    uninitialised: lores clamps them to 10 Hz and 1."""
+    KIND = None
+    CTOR = None  # setAttack, setDecay (ms), setSustain, setRelease (ms), pitch
+    USE_FILTER = False
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        V = self.V
+        self.inverse, self.useDistortion, self.useFilter, self.useLimiter = False, False, self.USE_FILTER, False
+        self.env = np.zeros((4, V))
+        self.holdtime = np.ones(V, np.int64)
+        self.pitch, self.distortion, self.gain = np.full(V, float(self.CTOR[4])), np.zeros(V), np.ones(V)
+        self.cutoff, self.resonance = np.zeros(V), np.zeros(V)
+        self.phase = DeviceBuffer(V)
+        self.dstate = DeviceBuffer((2, V))
+        self.istate = DeviceBuffer((6, V), np.int64)
+        self.fstate = DeviceBuffer((3, V))
+        self._dev = None
+        self.setAttack(self.CTOR[0])
+        self.setDecay(self.CTOR[1])
+        self.setSustain(self.CTOR[2])
+        self.setRelease(self.CTOR[3])
+
+    def _set(self, name, value):
+        getattr(self, name)[...] = np.asarray(value, getattr(self, name).dtype)
+        self._dev = None
+
+    def _coeff(self, which, ms):
+        f = lib().mxg_env_coeff_host
+        return np.array([f(which, m) for m in np.broadcast_to(np.asarray(ms, np.float64), (self.V,)).tolist()])
+
+    def setAttack(self, ms): self.env[0] = self._coeff(0, ms); self._dev = None    # (0: divides by zero inside pow, attack = 1)
+    def setDecay(self, ms): self.env[1] = self._coeff(1, ms); self._dev = None
+    def setSustain(self, level): self.env[2] = np.asarray(level, np.float64); self._dev = None
+    def setRelease(self, ms): self.env[3] = self._coeff(2, ms); self._dev = None
+    def setHoldtime(self, samples): self._set("holdtime", samples)
+    def setPitch(self, v): self._set("pitch", v)
+    def setDistortion(self, v): self._set("distortion", v)
+    def setCutoff(self, v): self._set("cutoff", v)
+    def setResonance(self, v): self._set("resonance", v)
+    def setGain(self, v): self._set("gain", v)
+
+    def flags(self):
+        return (DRUM_INVERSE if self.inverse else 0) | (DRUM_DISTORTION if self.useDistortion else 0) | \
+               (DRUM_FILTER if self.useFilter else 0) | (DRUM_LIMITER if self.useLimiter else 0)
+
+    def _coefs(self):
+        c = np.zeros((3, self.V))
+        check(lib().mxg_filter_coeffs_host(0, self.V, self.cutoff.ctypes.data, self.resonance.ctypes.data, c.ctypes.data), "mxg_filter_coeffs_host")
+        return c
+
+    def _params(self):
+        if self._dev is None:
+            self.host_coef = self._coefs()
+            self._dev = [DeviceBuffer.from_numpy(a) for a in (self.pitch, self.env, self.holdtime, self.distortion, self.host_coef, self.gain)]
+        return self._dev
+
+    def render(self, N, trig=None, rand=None, out=None):
+        """N x play() per voice.  trig: None (never triggered), or doubles [N] (one trigger signal for the bank) / [N][V], host or
+        device -- non-zero: trigger() before that play(); a maxiClockBank's tick block fits.  rand: int32 [N][V], the rand() draws
+        (snare and hats)."""
+        V, N = self.V, int(N)
+        tpv = 0
+        if trig is not None:
+            if not (isinstance(trig, DeviceBuffer) or hasattr(trig, "data_ptr")):
+                trig = DeviceBuffer.from_numpy(np.ascontiguousarray(trig, np.float64))
+            n = _fx_dev(trig, np.float64, "trig", (N, N * V))
+            tpv = 1 if n == N * V else 0   # (V == 1: the two layouts are one)
+        if rand is not None:
+            if not (isinstance(rand, DeviceBuffer) or hasattr(rand, "data_ptr")):
+                rand = DeviceBuffer.from_numpy(np.ascontiguousarray(rand, np.int32))
+            _fx_dev(rand, np.int32, "rand", (N * V,))
+        p = self._params()
+        out = self._out(N, out)
+        check(lib().mxg_drum_render(self.KIND, self.flags(), V, N, _ptr(trig), tpv, _ptr(rand), *[b.ptr for b in p], self.phase.ptr,
+                                    self.dstate.ptr, self.istate.ptr, self.fstate.ptr, _ptr(out), self.stream), "mxg_drum_render")
+        self._keep = (trig, rand)
+        return out
+
+
+class maxiKickBank(_DrumBank):
+    """V x maxiKick: sinewave(pitch*envOut)*envOut -> fastAtanDist -> lores -> limiter."""
+    KIND, CTOR = 0, (0, 1, 1.0, 500, 200.0)
+
+
+class maxiSnareBank(_DrumBank):
+    """V x maxiSnare: (triangle(pitch*(0.1+(envOut*0.85))) + noise())*envOut -> fastAtanDist -> lores (on by default) -> limiter."""
+    KIND, CTOR, USE_FILTER = 1, (0, 20, 0.05, 300, 800.0), True
+
+
+class maxiHatsBank(_DrumBank):
+    """V x maxiHats: (sinebuf(pitch) + noise())*envOut -> fastAtanDist -> maxiSVF::play(output, 0., 0., 1., 0.) -> limiter.  The SVF's
+    coefficients come from setFilterCutoff / setFilterResonance (the reference's filter.setCutoff / setResonance; the constructor:
+    8000, 1); cutoff / resonance exist and, as in the reference, are never read."""
+    KIND, CTOR = 2, (0, 20, 0.1, 300, 12000.0)
+
+    def __init__(self, voices, stream=None):
+        self.svf_cutoff, self.svf_resonance = np.full(int(voices), 8000.0), np.ones(int(voices))
+        super().__init__(voices, stream)
+
+    def setFilterCutoff(self, v): self._set("svf_cutoff", v)
+    def setFilterResonance(self, v): self._set("svf_resonance", v)
+
+    def _coefs(self):
+        c = np.zeros((5, self.V))
+        check(lib().mxg_svf_coeffs_host(self.V, self.svf_cutoff.ctypes.data, self.svf_resonance.ctypes.data, c.ctypes.data), "mxg_svf_coeffs_host")
+        return c
+
+
+class maxiClockBank(_Bank):
+    """V x maxiClock (src/libs/maxiClock.h; mxg_clock_render): render(N) is N x ticker() per voice and returns the tick block
+    [N][V] of 1.0 / 0.0, which a drum bank's render takes as `trig`.  State: clk [V] (timer.phase), playHead int64 [V]; lastCount
+    int32 [V] is only read; currentCount int32 [V] is what the last ticker() left."""
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        V = self.V
+        self.bpm, self.ticks = np.full(V, 120.0), np.ones(V, np.int32)
+        self.clk = DeviceBuffer(V)
+        self.playHead = DeviceBuffer(V, np.int64)
+        self.lastCount = DeviceBuffer(V, np.int32)
+        self.currentCount = DeviceBuffer(V, np.int32)
+        self.setTempo(self.bpm)
+
+    def setTempo(self, bpm):
+        self.bpm = np.ascontiguousarray(np.broadcast_to(np.asarray(bpm, np.float64), (self.V,))).copy()
+        self.bps = (self.bpm / 60.) * self.ticks
+        self._dbps = DeviceBuffer.from_numpy(self.bps)
+
+    def setTicksPerBeat(self, ticksPerBeat):
+        self.ticks = np.ascontiguousarray(np.broadcast_to(np.asarray(ticksPerBeat, np.int32), (self.V,))).copy()
+        self.setTempo(self.bpm)
+
+    def setLastCount(self, n):
+        self.lastCount.upload(np.broadcast_to(np.asarray(n, np.int32), (self.V,)))
+
+    def render(self, N, out=None):
+        out = self._out(int(N), out)
+        check(lib().mxg_clock_render(self.V, int(N), self._dbps.ptr, self.clk.ptr, self.lastCount.ptr, self.playHead.ptr,
+                                     self.currentCount.ptr, _ptr(out), self.stream), "mxg_clock_render")
+        return out

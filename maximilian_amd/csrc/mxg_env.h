@@ -11,6 +11,12 @@
 #define __device__
 #define __forceinline__ inline
 #endif
+// MXG_STEP_HOST_CALLABLE (a -D of the translation unit, csrc/Makefile: drums.hip): these functions also run on its host pass
+#if defined(__HIPCC__) && defined(MXG_STEP_HOST_CALLABLE)
+#define MXG_ENV_HD __host__ __device__ __forceinline__
+#else
+#define MXG_ENV_HD __device__ __forceinline__
+#endif
 
 namespace mxg {
 namespace {
@@ -22,7 +28,7 @@ struct Env {
     int attackphase, decayphase, sustainphase, holdphase, releasephase;
 };
 
-__device__ __forceinline__ void env_load(Env &e, size_t V, size_t v, const double *par,
+MXG_ENV_HD void env_load(Env &e, size_t V, size_t v, const double *par,
                                          const int64_t *holdtime, const double *dst,
                                          const int64_t *ist) {
     e.attack = par[v];
@@ -39,7 +45,7 @@ __device__ __forceinline__ void env_load(Env &e, size_t V, size_t v, const doubl
     e.holdphase = (int)ist[4 * V + v];
     e.releasephase = (int)ist[5 * V + v];
 }
-__device__ __forceinline__ void env_store(const Env &e, size_t V, size_t v, double *dst,
+MXG_ENV_HD void env_store(const Env &e, size_t V, size_t v, double *dst,
                                           int64_t *ist) {
     dst[v] = e.amplitude;
     dst[V + v] = e.output;
@@ -60,7 +66,7 @@ __device__ __forceinline__ void env_store(const Env &e, size_t V, size_t v, doub
 // output = input * g with g the amplitude at the LAST such statement that fired, or leaves output alone (upd = false) -- a select among
 // products of one input is the product with the selected factor, the same bits.  The state machine is this function; env_adsr
 // multiplies once.  The fused voice's two-stage form (voice.hip, voice_split_kernel) runs the gains a stage ahead of the filter.
-__device__ __forceinline__ double env_adsr_gain(Env &e, int trigger, bool &upd) {
+MXG_ENV_HD double env_adsr_gain(Env &e, int trigger, bool &upd) {
     const bool t1 = trigger == 1;
     // C:1417-1423
     const bool c1 = t1 && e.attackphase != 1 && e.holdphase != 1 && e.decayphase != 1;
@@ -108,7 +114,7 @@ __device__ __forceinline__ double env_adsr_gain(Env &e, int trigger, bool &upd) 
     upd = a || d || h || s || r;
     return g;
 }
-__device__ __forceinline__ double env_adsr(Env &e, double input, int trigger) {
+MXG_ENV_HD double env_adsr(Env &e, double input, int trigger) {
     bool upd;
     const double g = env_adsr_gain(e, trigger, upd);
     e.output = upd ? input * g : e.output;
@@ -121,21 +127,21 @@ __device__ __forceinline__ double env_adsr(Env &e, double input, int trigger) {
 // while it is > 0).  A wavefront whose lanes are all in one of them, with the (shared, scalar) gate
 // constant over a chunk, runs the chunk without the predicated state machine -- same operations on
 // the same values, so bit-identical, at ~1/6 of the VALU work.
-__device__ __forceinline__ bool env_in_sustain(const Env &e) {
+MXG_ENV_HD bool env_in_sustain(const Env &e) {
     return e.attackphase != 1 && e.decayphase != 1 && e.releasephase != 1 && e.holdphase == 1 &&
            e.holdcount >= e.holdtime;
 }
-__device__ __forceinline__ bool env_in_release(const Env &e) {
+MXG_ENV_HD bool env_in_release(const Env &e) {
     // holdphase == 0, not merely != 1: C:1456 stores 0 into it on every such sample, so any other value (a state
     // uploaded by the host) has to go through the state machine once
     return e.attackphase != 1 && e.decayphase != 1 && e.releasephase == 1 && e.holdphase == 0 &&
            e.holdcount >= e.holdtime;
 }
-__device__ __forceinline__ double env_sustain_tick(Env &e, double input) {  // gate == 1
+MXG_ENV_HD double env_sustain_tick(Env &e, double input) {  // gate == 1
     e.output = input * e.amplitude;  // C:1452
     return e.output;
 }
-__device__ __forceinline__ double env_release_tick(Env &e, double input) {  // gate != 1
+MXG_ENV_HD double env_release_tick(Env &e, double input) {  // gate != 1
     const bool r = e.amplitude > 0.;  // C:1460
     const double ampR = e.amplitude * e.release;
     e.amplitude = r ? ampR : e.amplitude;
@@ -160,7 +166,7 @@ __device__ __forceinline__ double env_release_tick(Env &e, double input) {  // g
 // instead of ~100.
 // (gain form, as env_adsr_gain: g[i] = the amplitude sample i multiplies its input by, upd = false for an idle lane, whose output stays)
 template <int U>
-__device__ __forceinline__ bool env_steady_gains(Env &e, const bool gate, double (&g)[U], bool &upd) {
+MXG_ENV_HD bool env_steady_gains(Env &e, const bool gate, double (&g)[U], bool &upd) {
     const bool ap = e.attackphase == 1, dp = e.decayphase == 1, hp = e.holdphase == 1, rp = e.releasephase == 1;
     const bool ge = e.holdcount >= e.holdtime;
     long long hb;
@@ -201,7 +207,7 @@ __device__ __forceinline__ bool env_steady_gains(Env &e, const bool gate, double
     return ok;
 }
 template <int U>
-__device__ __forceinline__ bool env_steady_chunk(Env &e, const double (&x)[U], const bool gate, double (&o)[U]) {
+MXG_ENV_HD bool env_steady_chunk(Env &e, const double (&x)[U], const bool gate, double (&o)[U]) {
     double g[U];
     bool upd;
     const bool ok = env_steady_gains<U>(e, gate, g, upd);
@@ -218,7 +224,7 @@ __device__ __forceinline__ bool env_steady_chunk(Env &e, const double (&x)[U], c
 // gate state of a full chunk from its (already fetched, wave-uniform) trigger values:
 // +1 all == 1, -1 all != 1, 0 mixed.  Scalar work.
 template <int U>
-__device__ __forceinline__ int gate_of_chunk(const int (&t)[U]) {
+MXG_ENV_HD int gate_of_chunk(const int (&t)[U]) {
     int on = 0;
 #pragma unroll
     for (int i = 0; i < U; i++) on += (t[i] == 1) ? 1 : 0;
@@ -226,7 +232,7 @@ __device__ __forceinline__ int gate_of_chunk(const int (&t)[U]) {
 }
 
 // C:1319-1358
-__device__ __forceinline__ double env_ar(Env &e, double input, int trigger) {
+MXG_ENV_HD double env_ar(Env &e, double input, int trigger) {
     const double attack = e.attack, release = e.release;
     const long long holdtime = e.holdtime;
     if (trigger == 1 && e.attackphase != 1 && e.holdphase != 1) {

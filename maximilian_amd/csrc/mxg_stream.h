@@ -40,9 +40,9 @@ __device__ __forceinline__ size_t bank_voice(size_t gid, size_t V) {
     return PX ? (gid < V ? gid : V - 2 + (gid & 1)) : live_voice(gid, V);
 }
 
-// rows 0 .. U-1 of the input stream p = in + v, before the loop
-template <int U>
-__device__ __forceinline__ void rows_first(double (&xn)[U], const double *__restrict__ p, size_t V, size_t N) {
+// rows 0 .. U-1 of the input stream p = in + v (doubles, or the int32 rand() draws), before the loop
+template <typename T, int U>
+__device__ __forceinline__ void rows_first(T (&xn)[U], const T *__restrict__ p, size_t V, size_t N) {
 #pragma unroll
     for (int i = 0; i < U; i++) {
         const size_t m = (size_t)i < N ? (size_t)i : N - 1;
@@ -51,8 +51,8 @@ __device__ __forceinline__ void rows_first(double (&xn)[U], const double *__rest
 }
 
 // at the top of chunk n0: xc = this chunk's rows, xn = the request for the next chunk's, a chunk ahead of the stores
-template <int U>
-__device__ __forceinline__ void rows_next(double (&xc)[U], double (&xn)[U], const double *__restrict__ p, size_t V, size_t N, size_t n0) {
+template <typename T, int U>
+__device__ __forceinline__ void rows_next(T (&xc)[U], T (&xn)[U], const T *__restrict__ p, size_t V, size_t N, size_t n0) {
 #pragma unroll
     for (int i = 0; i < U; i++) {
         xc[i] = xn[i];
