@@ -819,6 +819,64 @@ int mxg_clock_render(size_t V, size_t N, const double *d_bps, double *d_clk, con
 int mxg_clock_host(size_t V, size_t N, const double *h_bps, double *h_clk, const int32_t *h_lastcount, int64_t *h_playhead,
                    int32_t *h_count, double *h_tick);
 
+/* ---- maxiAtoms: Gabor atom banks, the atom queue and the book player (K22) ------------------------------------------------
+ * S independent streams, each one maxiAccelerator (src/libs/maxiAtoms.cpp:93-126) with, optionally, one maxiAtomBook and its
+ * maxiAtomBookPlayer (:198-219).  A bank owns per stream sampleIdx, atomIdx and a live list of at most Q queued atoms in queue order;
+ * a queued atom is GABOR (createGabor's parameters, :27-89, synthesised on the device from a float window table per distinct length)
+ * or RAW (floats of the bank's raw pool: what addAtom(flArr&) queues).
+ *   mxg_atoms_bank_create  h_book_start int64 [S + 1], rising from 0: stream s owns book atoms [start[s], start[s + 1]) (NULL: no
+ *                          books); h_book float [5][A] rows position, length, amp, frequency, phase as maxiGaborAtom holds them
+ *                          (A = start[S]); h_num_samples uint32 [S], the books' numSamples (>= 1); h_raw / raw_len the raw pool
+ *                          (may be empty; mxg_atoms_raw_append adds to it later and returns the offset).  All HOST arrays, copied.
+ *   mxg_atoms_add          n instances in order, HOST arrays: h_stream int32 [n]; h_kind [n] MXG_ATOM_GABOR / MXG_ATOM_RAW; h_length
+ *                          uint32 [n] the atom's size; h_offset uint32 [n] addAtom's offset (NULL: 0): startTime = sampleIdx + offset;
+ *                          h_par float [n][4] freq, sampleRate, startPhase, amp of createGabor (read for GABOR); h_raw_off uint32 [n]
+ *                          where a RAW atom's floats start in the pool.  Synchronises the device.  More than Q queued in a stream:
+ *                          MXG_ERR_INVALID and NOTHING is added.
+ *   mxg_atoms_fill         fillNextBuffer(buffer, N) on every stream: d_out float32 [S][N], each stream's buffer contiguous.
+ *                          accumulate != 0: the sum starts from what d_out holds (the reference's +=); 0: from zero.
+ *   mxg_atoms_play         maxiAtomBookPlayer::play(book, stream, ., N) and then the fill, in one call.  The player's offset is
+ *                          |looped - position| (the one deliberate departure).  A live list that would
+ *                          pass Q is reported through the asynchronous error word (mxg_last_async_error: MXG_ERR_INVALID) by the
+ *                          next call; that stream's block and state are left untouched, the other streams are rendered.
+ *   onset                  MXG_ATOM_ONSET_BLOCK: the reference's -- a due atom starts at buffer[0] of the block in which it falls
+ *                          due.  MXG_ATOM_ONSET_SAMPLE (an extension): it starts on its own sample, startTime - sampleIdx.
+ *   mxg_atoms_state        synchronises and copies out (any pointer may be NULL): sampleIdx int64 [S], atomIdx uint32 [S], the live
+ *                          counts int32 [S], and per live entry startTime int64 / pos uint32 / size uint32, each [S][Q].
+ *   mxg_atoms_gabor_host   createGabor on the host: length floats.
+ * RAW atoms are BIT-EXACT in either onset mode: a float sum in queue order.  GABOR atoms: every operation but the sine is the
+ * reference's; the sine is the correctly reduced double sine rounded to float, within 1 float ULP of glibc's sinf (DESIGN.md
+ * section 4), and the device result is bit-identical to the _host twin's.
+ * DOMAIN: Gabor lengths in [1, 22 050) (the reference's window cache); finite parameters; |maxPhase| + |startPhase| <= 2^19 rad;
+ * N <= 2^24; sample indices below 2^31 (the reference narrows startTime + pos to int).
+ * The _host twins: the same calls on a bank made by mxg_atoms_bank_create_host, whose arrays -- and h_out -- are host memory; the
+ * same functions (csrc/mxg_atoms.h) on the CPU, no device needed.  mxg_atoms_play_host returns the overflow itself.
+ * mxg_atoms_bank_destroy, mxg_atoms_raw_append and mxg_atoms_state take both kinds of bank. */
+#define MXG_ATOM_GABOR 0
+#define MXG_ATOM_RAW 1
+#define MXG_ATOM_KINDS 2
+#define MXG_ATOM_ONSET_BLOCK 0
+#define MXG_ATOM_ONSET_SAMPLE 1
+#define MXG_ATOMS_PIECE 64 /* segments of a stream's block staged through LDS at a time (K22b) */
+typedef struct mxg_atoms_bank mxg_atoms_bank;
+mxg_atoms_bank *mxg_atoms_bank_create(size_t S, size_t Q, const int64_t *h_book_start, const float *h_book,
+                                      const uint32_t *h_num_samples, const float *h_raw, size_t raw_len);
+mxg_atoms_bank *mxg_atoms_bank_create_host(size_t S, size_t Q, const int64_t *h_book_start, const float *h_book,
+                                           const uint32_t *h_num_samples, const float *h_raw, size_t raw_len);
+int mxg_atoms_bank_destroy(mxg_atoms_bank *b);
+int mxg_atoms_raw_append(mxg_atoms_bank *b, const float *h_raw, size_t n, uint32_t *offset);
+int mxg_atoms_add(mxg_atoms_bank *b, size_t n, const int32_t *h_stream, const int32_t *h_kind, const uint32_t *h_length,
+                  const uint32_t *h_offset, const float *h_par, const uint32_t *h_raw_off);
+int mxg_atoms_add_host(mxg_atoms_bank *b, size_t n, const int32_t *h_stream, const int32_t *h_kind, const uint32_t *h_length,
+                       const uint32_t *h_offset, const float *h_par, const uint32_t *h_raw_off);
+int mxg_atoms_fill(mxg_atoms_bank *b, size_t N, float *d_out, int onset, int accumulate, void *stream);
+int mxg_atoms_play(mxg_atoms_bank *b, size_t N, float *d_out, int onset, int accumulate, void *stream);
+int mxg_atoms_fill_host(mxg_atoms_bank *b, size_t N, float *h_out, int onset, int accumulate);
+int mxg_atoms_play_host(mxg_atoms_bank *b, size_t N, float *h_out, int onset, int accumulate);
+int mxg_atoms_state(mxg_atoms_bank *b, int64_t *h_sample_idx, uint32_t *h_atom_idx, int32_t *h_nlive, int64_t *h_start,
+                    uint32_t *h_pos, uint32_t *h_size);
+int mxg_atoms_gabor_host(float freq, float sample_rate, uint32_t length, float start_phase, float amp, float *h_atom);
+
 /* ---- maxiSample play family -------------------------------------------------------------- */
 typedef enum {
     MXG_SMP_PLAY = 0,                    /* play()                       C:740-747   */

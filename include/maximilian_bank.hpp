@@ -1247,6 +1247,75 @@ private:
     maxigpu::DeviceArray<int32_t> d_last_, d_count_;
 };
 
+// S x (maxiAccelerator + maxiAtomBook + maxiAtomBookPlayer) (src/libs/maxiAtoms.h; kernel K22, mxg_atoms_*): every stream owns a queue of
+// at most `capacity` live atoms and, optionally, a book.  fillNextBuffer / play write the float32 block [S][N] on the device, each
+// stream's buffer contiguous; accumulate: the sum starts from what d_out holds (the reference's +=).  onset MXG_ATOM_ONSET_BLOCK is the
+// reference's, MXG_ATOM_ONSET_SAMPLE (an extension) starts a due atom on its own sample.
+class maxiAtomBank {
+public:
+    struct BookAtom {  // what a maxiGaborAtom holds
+        float position, length, amp, frequency, phase;
+    };
+    maxiAtomBank(size_t streams, size_t capacity, const std::vector<std::vector<BookAtom>> &books = {}, const std::vector<uint32_t> &numSamples = {},
+                 const std::vector<float> &raw = {})
+        : S(streams), Q(capacity) {
+        std::vector<int64_t> start(S + 1, 0);
+        if (!books.empty() && books.size() != S) throw std::runtime_error("maxiAtomBank: one book per stream");
+        for (size_t s = 0; s < S && !books.empty(); s++) start[s + 1] = start[s] + (int64_t)books[s].size();
+        const size_t A = (size_t)start[S];
+        std::vector<float> rows(5 * A);
+        for (size_t s = 0, k = 0; s < S && !books.empty(); s++)
+            for (const BookAtom &a : books[s]) {
+                rows[k] = a.position, rows[A + k] = a.length, rows[2 * A + k] = a.amp, rows[3 * A + k] = a.frequency, rows[4 * A + k] = a.phase;
+                k++;
+            }
+        std::vector<uint32_t> ns(S, 1);
+        for (size_t s = 0; s < S && s < numSamples.size(); s++) ns[s] = numSamples[s];
+        h_ = mxg_atoms_bank_create(S, Q, start.data(), rows.data(), ns.data(), raw.data(), raw.size());
+        if (!h_) throw std::runtime_error(std::string("mxg_atoms_bank_create: ") + mxg_last_error());
+    }
+    ~maxiAtomBank() { mxg_atoms_bank_destroy(h_); }
+    maxiAtomBank(const maxiAtomBank &) = delete;
+    maxiAtomBank &operator=(const maxiAtomBank &) = delete;
+    size_t streams() const { return S; }
+    uint32_t appendRaw(const std::vector<float> &floats) {
+        uint32_t at = 0;
+        maxigpu::check(mxg_atoms_raw_append(h_, floats.data(), floats.size(), &at), "mxg_atoms_raw_append");
+        return at;
+    }
+    // addAtom(atom, offset) on one stream: a raw atom of `length` floats from the pool ...
+    void addAtom(int32_t stream, uint32_t rawOffset, uint32_t length, uint32_t offset = 0) {
+        const int32_t kind = MXG_ATOM_RAW;
+        maxigpu::check(mxg_atoms_add(h_, 1, &stream, &kind, &length, &offset, nullptr, &rawOffset), "mxg_atoms_add");
+    }
+    // ... or createGabor's arguments, synthesised on the device
+    void addGabor(int32_t stream, float freq, float sampleRate, uint32_t length, float startPhase, float amp, uint32_t offset = 0) {
+        const int32_t kind = MXG_ATOM_GABOR;
+        const float par[4] = {freq, sampleRate, startPhase, amp};
+        maxigpu::check(mxg_atoms_add(h_, 1, &stream, &kind, &length, &offset, par, nullptr), "mxg_atoms_add");
+    }
+    void fillNextBuffer(size_t N, float *d_out, int onset = MXG_ATOM_ONSET_BLOCK, bool accumulate = true, void *stream = nullptr) {
+        maxigpu::check(mxg_atoms_fill(h_, N, d_out, onset, accumulate ? 1 : 0, stream), "mxg_atoms_fill");
+    }
+    void play(size_t N, float *d_out, int onset = MXG_ATOM_ONSET_BLOCK, bool accumulate = true, void *stream = nullptr) {
+        maxigpu::check(mxg_atoms_play(h_, N, d_out, onset, accumulate ? 1 : 0, stream), "mxg_atoms_play");
+    }
+    std::vector<int64_t> sampleIdx() const {
+        std::vector<int64_t> v(S);
+        maxigpu::check(mxg_atoms_state(h_, v.data(), nullptr, nullptr, nullptr, nullptr, nullptr), "mxg_atoms_state");
+        return v;
+    }
+    std::vector<int32_t> liveCount() const {
+        std::vector<int32_t> v(S);
+        maxigpu::check(mxg_atoms_state(h_, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr), "mxg_atoms_state");
+        return v;
+    }
+
+private:
+    size_t S, Q;
+    mxg_atoms_bank *h_ = nullptr;
+};
+
 // ---- sequencers (H:564-596, 1953-2013, 2093-2262; kernel K15): what tells the other banks WHEN ----------------------
 namespace maxigpu {
 // lists of doubles as the table form of mxg_seq_render / mxg_seq_signal: doubles [P][L] + int32 lengths [P] on the device

@@ -15,6 +15,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
                     maxiPolyBLEPBank, polyblep_sync, POLYBLEP_WAVEFORMS,
                     maxiKickBank, maxiSnareBank, maxiHatsBank, maxiClockBank, DRUM_KINDS,
+                    maxiAtomBank, ATOM_KINDS, ATOM_ONSETS,
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import (maxiConvolve, maxiFFT, maxiIFFT, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
                        padded_stream)

@@ -136,6 +136,18 @@ SIGNATURES = {
     "mxg_drum_host": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_int] + [c_void_p] * 12),
     "mxg_clock_render": (c_int, [c_size_t, c_size_t] + [c_void_p] * 7),
     "mxg_clock_host": (c_int, [c_size_t, c_size_t] + [c_void_p] * 6),
+    "mxg_atoms_bank_create": (c_void_p, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "mxg_atoms_bank_create_host": (c_void_p, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "mxg_atoms_bank_destroy": (c_int, [c_void_p]),
+    "mxg_atoms_raw_append": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_uint32)]),
+    "mxg_atoms_add": (c_int, [c_void_p, c_size_t] + [c_void_p] * 6),
+    "mxg_atoms_add_host": (c_int, [c_void_p, c_size_t] + [c_void_p] * 6),
+    "mxg_atoms_fill": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p]),
+    "mxg_atoms_play": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p]),
+    "mxg_atoms_fill_host": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int]),
+    "mxg_atoms_play_host": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int]),
+    "mxg_atoms_state": (c_int, [c_void_p] * 7),
+    "mxg_atoms_gabor_host": (c_int, [c_float, c_float, c_uint32, c_float, c_float, c_void_p]),
     "mxg_sample_upload": (c_void_p, [c_void_p, c_size_t]),
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,

@@ -2032,3 +2032,94 @@ class maxiClockBank(_Bank):
         check(lib().mxg_clock_render(self.V, int(N), self._dbps.ptr, self.clk.ptr, self.lastCount.ptr, self.playHead.ptr,
                                      self.currentCount.ptr, _ptr(out), self.stream), "mxg_clock_render")
         return out
+
+
+ATOM_KINDS = {"gabor": 0, "raw": 1}
+ATOM_ONSETS = {"block": 0, "sample": 1}
+
+
+class maxiAtomBank:
+    """S x (maxiAccelerator + maxiAtomBook + maxiAtomBookPlayer) (src/libs/maxiAtoms.h; K22, mxg_atoms_*).  Every stream owns a queue
+    of at most `capacity` live atoms; `books` gives stream s its book as rows (position, length, amp, frequency, phase) -- what a
+    maxiGaborAtom holds -- and `num_samples` the books' numSamples.  `raw` is the pool of floats that raw atoms (addAtom(flArr&)) read.
+
+    fillNextBuffer(N) and play(N) return the float32 block [S][N] on the device, each stream's buffer contiguous; `out` is added to
+    when accumulate is true (the reference's buffer[i] += ...).  onset "block" is the reference's: a due atom starts on the first sample
+    of the block in which it falls due; "sample" (an extension) starts it on its own sample."""
+
+    def __init__(self, streams, capacity=256, books=None, num_samples=None, raw=None, stream=None):
+        check(lib().mxg_init(-1), "mxg_init")
+        self.S, self.Q, self.stream = int(streams), int(capacity), stream
+        starts = np.zeros(self.S + 1, np.int64)
+        rows = [np.zeros((0, 5), np.float32)] * self.S
+        if books is not None:
+            assert len(books) == self.S, "one book per stream"
+            rows = [np.asarray(b, np.float32).reshape(-1, 5) for b in books]
+        for s, b in enumerate(rows):
+            starts[s + 1] = starts[s] + len(b)
+        book = np.ascontiguousarray(np.concatenate(rows, axis=0).T)
+        ns = np.ascontiguousarray(np.broadcast_to(np.asarray(1 if num_samples is None else num_samples, np.uint32), (self.S,)))
+        pool = np.zeros(0, np.float32) if raw is None else np.ascontiguousarray(raw, np.float32).ravel()
+        self._h = lib().mxg_atoms_bank_create(self.S, self.Q, starts.ctypes.data, book.ctypes.data, ns.ctypes.data, pool.ctypes.data, len(pool))
+        if not self._h:
+            raise ValueError("mxg_atoms_bank_create: %s" % lib().mxg_last_error().decode())
+
+    def appendRaw(self, floats):
+        """Adds floats to the raw pool; returns where they start."""
+        a = np.ascontiguousarray(floats, np.float32).ravel()
+        off = ctypes.c_uint32(0)
+        check(lib().mxg_atoms_raw_append(self._h, a.ctypes.data, len(a), ctypes.byref(off)), "mxg_atoms_raw_append")
+        return off.value
+
+    def _add(self, stream, kind, length, offset, par, raw_off):
+        n = len(stream)
+        a = [np.ascontiguousarray(x, t) for x, t in ((stream, np.int32), (kind, np.int32), (length, np.uint32), (offset, np.uint32),
+                                                     (par, np.float32), (raw_off, np.uint32))]
+        check(lib().mxg_atoms_add(self._h, n, *[x.ctypes.data for x in a]), "mxg_atoms_add")
+
+    def addAtom(self, stream, raw_offset, length, offset=0):
+        """addAtom(atom, offset) for raw atoms: arrays (or scalars) over the instances, queued in order."""
+        stream = np.atleast_1d(np.asarray(stream, np.int32))
+        n = len(stream)
+        bc = lambda x, t: np.broadcast_to(np.asarray(x, t), (n,))
+        self._add(stream, np.full(n, ATOM_KINDS["raw"]), bc(length, np.uint32), bc(offset, np.uint32), np.zeros((n, 4)), bc(raw_offset, np.uint32))
+
+    def addGabor(self, stream, freq, length, startPhase=0.0, amp=1.0, offset=0, sampleRate=44100.0):
+        """addAtom(createGabor(freq, sampleRate, length, startPhase, ., amp), offset): the atom is synthesised on the device."""
+        stream = np.atleast_1d(np.asarray(stream, np.int32))
+        n = len(stream)
+        bc = lambda x, t: np.broadcast_to(np.asarray(x, t), (n,))
+        par = np.stack([bc(freq, np.float32), bc(sampleRate, np.float32), bc(startPhase, np.float32), bc(amp, np.float32)], axis=1)
+        self._add(stream, np.full(n, ATOM_KINDS["gabor"]), bc(length, np.uint32), bc(offset, np.uint32), par, np.zeros(n))
+
+    def _step(self, fn, what, N, out, onset, accumulate):
+        N = int(N)
+        if out is None:
+            out, accumulate = DeviceBuffer((self.S, N), np.float32, zero=False), False
+        check(fn(self._h, N, _ptr(out), ATOM_ONSETS[onset] if isinstance(onset, str) else int(onset), int(bool(accumulate)), self.stream), what)
+        return out
+
+    def fillNextBuffer(self, N, out=None, onset="block", accumulate=True):
+        return self._step(lib().mxg_atoms_fill, "mxg_atoms_fill", N, out, onset, accumulate)
+
+    def play(self, N, out=None, onset="block", accumulate=True):
+        return self._step(lib().mxg_atoms_play, "mxg_atoms_play", N, out, onset, accumulate)
+
+    def state(self):
+        """sampleIdx [S], atomIdx [S], and per stream the live entries (startTime, pos, size) in queue order.  Synchronises."""
+        S, Q = self.S, self.Q
+        idx, ai, nl = np.zeros(S, np.int64), np.zeros(S, np.uint32), np.zeros(S, np.int32)
+        start, pos, size = np.zeros((S, Q), np.int64), np.zeros((S, Q), np.uint32), np.zeros((S, Q), np.uint32)
+        check(lib().mxg_atoms_state(self._h, *[x.ctypes.data for x in (idx, ai, nl, start, pos, size)]), "mxg_atoms_state")
+        return idx, ai, [[(int(start[s, k]), int(pos[s, k]), int(size[s, k])) for k in range(nl[s])] for s in range(S)]
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().mxg_atoms_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # best effort
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -100,6 +100,7 @@ enum AsyncError {
     ASYNC_OK = 0,
     ASYNC_GRAIN_BASE = 100,   // + the granular render's code 1..5 (grains.hip)
     ASYNC_PART_TIMEOUT = 16,  // part_wait gave up: the state of that launch was NOT stored
+    ASYNC_ATOMS_OVERFLOW = 32,  // the book player would queue more than Q atoms in a stream (atoms.hip): that stream was left untouched
 };
 int *async_error_word();  // device-visible address of the word (valid after mxg_init)
 int async_error_poll();   // host: MXG_OK, or the pending error as a status (+ message), cleared

@@ -195,6 +195,9 @@ int async_error_status(int code) {
         return fail(MXG_ERR_HIP, "asynchronous device error: a time-split kernel (osc / sample *AtSpeed) timed out waiting for its "
                                  "sibling parts; the per-voice state of that launch was not stored");
     }
+    if (code == ASYNC_ATOMS_OVERFLOW)
+        return fail(MXG_ERR_INVALID, "mxg_atoms_play: the book player queued more than Q atoms in a stream; that stream's block and state "
+                                     "were left untouched");
     switch (code - ASYNC_GRAIN_BASE) {
         case 1: return fail(MXG_ERR_INVALID, "mxg_granular_render: more than 8 grains alive in a stream");
         case 2: return fail(MXG_ERR_INVALID, "mxg_granular_render: d_rnd exhausted (R too small)");
