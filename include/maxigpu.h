@@ -126,7 +126,8 @@ int mxg_prof_overhead_ms(void *stream, int pairs, double *h_ms);
 
 /* ---- tuning knobs (performance only; results are identical for every setting) ---------- */
 /* key: "osc_vpl" (voices per lane: 0 automatic, 1|2), "osc_block" (64..1024), "osc_nt" (non-temporal stores: 0 never, 1 always, 2 by the size of the output block),
- * "voice_block", "voice_nt" (as osc_nt), "mix_rows" (sample rows per workgroup of the mixdown, 1|2), "fft_generic",
+ * "voice_block" (lanes per workgroup of the one-lane-per-voice bank kernels: a multiple of 64, capped at 256; the polyblep, drum, clock, line and
+ * analysis banks run at 64 up to 16 384 voices whatever the knob says; bit-identical results at every value), "voice_nt" (as osc_nt), "mix_rows" (sample rows per workgroup of the mixdown, 1|2), "fft_generic",
  * "mfcc_tiled" (LDS-staged spectra 0|1), "grain_chunked" (time-sharded granular render 0|1), "grain_lanes_k",
  * "grain_unit" (coalesced unit-increment render 0|1), "grain_line" (tile render for arbitrary increments 0|1), "grain_fast_sched" (event-driven schedulers 0|1), "grain_streamed" (unit-path maxiTimeStretch call as ONE launch whose scheduler lanes
  * and tile renders run side by side, 1 default; 0 = time slices on the library's auxiliary streams), "grain_slices" (those time slices, 1..16), "osc_mix_win" (K1m: samples per workgroup combine window, 0 automatic, 128 or 256), "osc_mix_pcwin" (the same for the producer / consumer form: 0 automatic, 256 or 512), "osc_mix_pc" (K1m as producer / consumer wavefront pairs: 0 automatic, 1 off, 2 on),

@@ -76,9 +76,10 @@ __device__ __forceinline__ void emit_rows(double *&op, size_t V, const double (&
     }
 }
 
-// The workgroup of a per-voice kernel: the knob voice_block, at most 256 lanes (the kernels are compiled with
-// __launch_bounds__(256)).  small64: banks of up to 16 384 voices run in workgroups of one wavefront, so that they still spread
-// over the compute units (dyn.hip).
+// The workgroup of a per-voice kernel: the knob voice_block (mxg_tune takes 64 .. 1024 in multiples of 64), at most 256 lanes (the
+// kernels are compiled with __launch_bounds__(256)): 64, 128, 192 or 256.  small64: banks of up to 16 384 voices run in workgroups
+// of one wavefront, so that they still spread over the compute units -- polyblep_kernel, drum_kernel and clock_kernel, line_kernel
+// (shaper.hip) and analysis_kernel pass true.  tests/test_gpu_workgroups.py runs every caller at every size.
 inline int voice_block(size_t V, bool small64 = false) {
     int block = tune_get("voice_block");
     if (block > 256) block = 256;

@@ -269,7 +269,8 @@ def fastatan(x):
 
 
 def kick_bound(L, variant, env_out, n=N):
-    """[n]: the absolute bound of the kick's output at every sample (module docstring); env_out [n] is the envelope's output."""
+    """[n]: the absolute bound of the kick's output at every sample (module docstring); env_out [n] is the envelope's output.
+    env_out [n][V] (one envelope per voice, the case's other parameters on every voice) gives the bound [n][V]."""
     c, fl = CASES[("kick", variant)], flags_of("kick", variant)
     u = 2.0 ** -53
     D, ops = 1.0, 1   # ops: roundings after the sine (the product with envOut)
@@ -291,7 +292,10 @@ def kick_bound(L, variant, env_out, n=N):
             x = x * r
             h[k] = y
         H = np.abs(h)
-        e = np.convolve(e, H)[:n]
+        if e.ndim == 1:
+            e = np.convolve(e, H)[:n]
+        else:   # the same convolution down every column
+            e = np.sum([np.concatenate([np.zeros((k,) + e.shape[1:]), H[k] * e[:n - k]]) for k in range(n)], axis=0)
         ops += 5
         peak *= H.sum()
     return (e + ops * u * peak) * c["gain"] + u * peak * c["gain"]

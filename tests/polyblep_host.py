@@ -281,11 +281,16 @@ def play_case(be, g, wf, cuts=None, tile=1, fps=None, voices=None, upto=N, pw_no
 def check_contract(g, wf, out, phases, what="", tile=1, voices=None):
     """DESIGN.md section 4 against the stored reference (its first out.shape[0] samples, the voices spread as in play_case);
     returns the measured maxima {ulp, abs} for the printout."""
-    from conftest import assert_bits_equal, ulp_diff
     n = out.shape[0]
-    ref = _spread(ref_out(g, wf), tile, voices)[:n]
-    fb = _spread(fallback(freqs(g)), tile, voices)[:n]
-    assert_bits_equal(phases, _spread(g["t/" + wf], tile, voices)[:phases.shape[0]], "%s %s: phase" % (what, wf))
+    return check_against(wf, out, phases, _spread(ref_out(g, wf), tile, voices)[:n],
+                         _spread(g["t/" + wf], tile, voices)[:phases.shape[0]], _spread(fallback(freqs(g)), tile, voices)[:n], what)
+
+
+def check_against(wf, out, phases, ref, ref_phases, fb, what=""):
+    """The same contract against any expectation of the same shapes (the stored reference, or mxg_polyblep_host on voices the file
+    does not hold): `fb` marks the samples that fall back to the sine.  Returns the measured maxima {ulp, abs}."""
+    from conftest import assert_bits_equal, ulp_diff
+    assert_bits_equal(phases, ref_phases, "%s %s: phase" % (what, wf))
     res = {"ulp": 0, "abs": 0.0}
     if fb.any():
         res["ulp"] = int(ulp_diff(out[fb], ref[fb]).max())
