@@ -741,6 +741,88 @@ int mxg_line_prepare_host(size_t V, const double *h_start, const double *h_end, 
 int mxg_line_render(size_t V, size_t N, const double *d_trig, double trig_const, const double *d_par, double *d_st, double *d_out,
                     void *stream);
 
+/* ---- the classic core classes: maxiDyn, maxiEnvelope, maxiLagExp<double>, maxiMap, maxiConvert (K23) -------------------------
+ * (src/maximilian.cpp:377-412, 1200-1314; src/maximilian.h:499-560, 801-854, 955-961.)  All blocks are [N][V] doubles.  The
+ * sample rate in force is mxg_settings's.  Every mxg_*_render below has a twin mxg_*_host with the same arguments but the stream,
+ * which runs the same arithmetic (maximilian_amd/csrc/mxg_classic.h) on HOST arrays and needs no device.
+ *
+ * mxg_dyn_gate_render: d_out[n][v] = bank[v].gate(d_in[n][v], threshold, holdtime, attack, release) (C:1200-1235).  BIT-EXACT, the
+ * state included.  mxg_dyn_compress_render: maxiDyn::compressor(input, ratio, threshold, attack, release) (C:1238-1267); d_makeup
+ * is 1 + log(ratio) from mxg_dyn_makeup_host (the host libm, the reference's expression), in the layout of d_ratio: the device
+ * path has no transcendental and is BIT-EXACT.  maxiDyn::compress(input) (C:1269-1298) is the same step with the object's own
+ * members as parameters; note that setAttack stores mxg_dyn_coeff_host(ms, sample_rate) = pow(0.01, 1.0 / (ms * sr * 0.001)),
+ * which compress() then uses as 1 + attack (kept).
+ *   d_threshold, d_attack, d_release, d_ratio (+ d_makeup): [V], or [N][V] where their MXG_CLASSIC_PS_* bit is set in ps_flags
+ *   (ratio and makeup travel together); d_holdtime int64 [V].
+ *   State, in/out, shared by gate and compressor as the members of one maxiDyn are: d_dst double [3][V] = amplitude,
+ *   currentRatio, output; d_ist int64 [4][V] = holdcount, attackphase, holdphase, releasephase.  Fresh objects: all zero.
+ *   d_out is distinct from d_in.
+ *
+ * mxg_envelope_line_render: d_out[n][v] = bank[v].line(d_count[v], segments of voice v) (C:377-402).  d_segments [S][V], S = 2 ..
+ * 64 entries (value, time, value, time ...), d_count int32 [V] = numberofsegments.  d_trig: NULL, or a block [N][V]: a non-zero
+ * value at sample n performs trigger(d_trig_index[v], d_trig_amp[v]) (C:407-412) before that sample's line().  State, in/out:
+ * d_dst double [2][V] = amplitude, startval; d_ist int32 [2][V] = valindex, isPlaying.  Fresh objects: all zero (output 0 until
+ * triggered).  BIT-EXACT, the state included; a zero segment time gives the reference's IEEE infinities and NaNs.  The
+ * reference's reads past its table (segments[valindex + 2], and segments[n], segments[n + 1] for one call after the last
+ * segment) reach no result and are not made.  One defined departure: every table index is held inside [0, count - 1] and a
+ * trigger index inside [0, count - 2], where the reference would index out of its vector (d_count itself is held inside
+ * [1, S]; a legal one is 2 .. S).  d_out is distinct from d_trig.
+ * mxg_envelope_trigger_host: trigger(h_index[v], h_amp[v]) on HOST copies of d_dst / d_ist for the voices whose h_mask is
+ * non-zero (NULL: all); an index outside [0, h_count[v] - 2] is refused and nothing is changed.
+ *
+ * mxg_lag_render: val = (alpha * x) + (alphaReciprocal * val) (H:523-526), d_out[n][v] = the new val.  d_alpha and
+ * d_alpha_reciprocal are independent ([V], or both [N][V] with alpha_per_sample); d_val [V] in/out.  BIT-EXACT.  d_out is
+ * distinct from d_in.
+ *
+ * mxg_map_render: stateless and flat over the N * V elements like mxg_shape_render; d_out == d_in is allowed.  d_range [4][V] =
+ * inMin, inMax, outMin, outMax per voice.  The clip is max(min(val, inMax), inMin) as the reference's compares: a NaN passes.
+ *     MXG_MAP_LINLIN                                                                                            BIT-EXACT
+ *     MXG_MAP_LINEXP    the device's pow                                                             tolerance, DESIGN.md
+ *     MXG_MAP_EXPLIN    d_aux [V] = log(inMax / inMin) from mxg_map_range_host; the device's log     tolerance, DESIGN.md
+ *     MXG_MAP_CLAMP     d_range rows 0, 1 = low, high ([2][V] is enough)                                        BIT-EXACT
+ *     MXG_MAP_AMPTODBS  log10(x) * 20.0, no range (d_range may be NULL); the device's log10          tolerance, DESIGN.md
+ *     MXG_MAP_DBSTOAMP  pow(10.0, x * 0.05), no range; the device's pow                              tolerance, DESIGN.md
+ * Positions of NaN and +-Inf are the reference's in every mode.
+ * mxg_map_range_host: h_aux [V] for `mode` from a host copy of d_range (explin: log(inMax / inMin) with the host libm; else 0). */
+#define MXG_MAP_LINLIN 0
+#define MXG_MAP_LINEXP 1
+#define MXG_MAP_EXPLIN 2
+#define MXG_MAP_CLAMP 3
+#define MXG_MAP_AMPTODBS 4
+#define MXG_MAP_DBSTOAMP 5
+#define MXG_MAP_MODES 6
+#define MXG_ENVELOPE_MAX_S 64
+#define MXG_CLASSIC_PS_THRESHOLD 1
+#define MXG_CLASSIC_PS_ATTACK 2
+#define MXG_CLASSIC_PS_RELEASE 4
+#define MXG_CLASSIC_PS_RATIO 8
+#define MXG_CLASSIC_PS_MASK 15
+double mxg_dyn_coeff_host(double ms, double sample_rate);
+double mxg_dyn_makeup_host(double ratio);
+int mxg_dyn_gate_render(size_t V, size_t N, const double *d_in, const double *d_threshold, const double *d_attack, const double *d_release,
+                        int ps_flags, const int64_t *d_holdtime, double *d_dst, int64_t *d_ist, double *d_out, void *stream);
+int mxg_dyn_gate_host(size_t V, size_t N, const double *h_in, const double *h_threshold, const double *h_attack, const double *h_release,
+                      int ps_flags, const int64_t *h_holdtime, double *h_dst, int64_t *h_ist, double *h_out);
+int mxg_dyn_compress_render(size_t V, size_t N, const double *d_in, const double *d_ratio, const double *d_makeup, const double *d_threshold,
+                            const double *d_attack, const double *d_release, int ps_flags, double *d_dst, int64_t *d_ist, double *d_out,
+                            void *stream);
+int mxg_dyn_compress_host(size_t V, size_t N, const double *h_in, const double *h_ratio, const double *h_makeup, const double *h_threshold,
+                          const double *h_attack, const double *h_release, int ps_flags, double *h_dst, int64_t *h_ist, double *h_out);
+int mxg_envelope_trigger_host(size_t V, const int32_t *h_index, const double *h_amp, const int32_t *h_mask, const int32_t *h_count,
+                              double *h_dst, int32_t *h_ist);
+int mxg_envelope_line_render(size_t V, size_t N, size_t S, const double *d_segments, const int32_t *d_count, const double *d_trig,
+                             const int32_t *d_trig_index, const double *d_trig_amp, double *d_dst, int32_t *d_ist, double *d_out,
+                             void *stream);
+int mxg_envelope_line_host(size_t V, size_t N, size_t S, const double *h_segments, const int32_t *h_count, const double *h_trig,
+                           const int32_t *h_trig_index, const double *h_trig_amp, double *h_dst, int32_t *h_ist, double *h_out);
+int mxg_lag_render(size_t V, size_t N, const double *d_in, const double *d_alpha, const double *d_alpha_reciprocal, int alpha_per_sample,
+                   double *d_val, double *d_out, void *stream);
+int mxg_lag_host(size_t V, size_t N, const double *h_in, const double *h_alpha, const double *h_alpha_reciprocal, int alpha_per_sample,
+                 double *h_val, double *h_out);
+int mxg_map_range_host(int mode, size_t V, const double *h_range, double *h_aux);
+int mxg_map_render(int mode, size_t V, size_t N, const double *d_in, const double *d_range, const double *d_aux, double *d_out, void *stream);
+int mxg_map_host(int mode, size_t V, size_t N, const double *h_in, const double *h_range, const double *h_aux, double *h_out);
+
 /* ---- maxiPolyBLEP: the anti-aliased oscillator (K20) --------------------------------------------------------------------
  * V x maxiPolyBLEP::play(freq) (src/libs/maxiPolyBLEP.h over src/libs/PolyBLEP/PolyBLEP.cpp): per sample dt = freq / sample_rate,
  * the waveform's sample on the phase t -- or a sine where (freq / sample_rate) * sample_rate >= sample_rate / 4 -- then

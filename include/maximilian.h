@@ -1425,6 +1425,131 @@ public:
     inline T value() const { return val; }
 };
 
+// ---- maxiDyn (H:858-884; C:1200-1314), maxiEnvelope (H:220-260; C:377-412): the two classes the reference calls deprecated and
+// still ships.  Host value types like maxiLine: plain arithmetic a patch calls once per sample, the same statements as the banks'
+// (maximilian_amd/csrc/mxg_classic.h, kernel K23) -- the reference's bits; log and pow are the host libm's, as in the reference.
+// Members the reference leaves uninitialised start at zero (static-storage semantics).
+class maxiDyn {
+public:
+    double gate(double input, double threshold = 0.9, long holdtime = 1, double attack = 1, double release = 0.9995) {  // C:1200-1235
+        if (fabs(input) > threshold && attackphase != 1) {
+            holdcount = 0;
+            releasephase = 0;
+            attackphase = 1;
+            if (amplitude == 0) amplitude = 0.01;
+        }
+        if (attackphase == 1 && amplitude < 1) {
+            amplitude *= (1 + attack);
+            output = input * amplitude;
+        }
+        if (amplitude >= 1) {
+            attackphase = 0;
+            holdphase = 1;
+        }
+        if (holdcount < holdtime && holdphase == 1) {
+            output = input;
+            holdcount++;
+        }
+        if (holdcount == holdtime) {
+            holdphase = 0;
+            releasephase = 1;
+        }
+        if (releasephase == 1 && amplitude > 0.) {
+            output = input * (amplitude *= release);
+        }
+        return output;
+    }
+    double compressor(double input, double ratio, double threshold = 0.9, double attack = 1, double release = 0.9995) {  // C:1238-1267
+        if (fabs(input) > threshold && attackphase != 1) {
+            holdcount = 0;
+            releasephase = 0;
+            attackphase = 1;
+            if (currentRatio == 0) currentRatio = ratio;
+        }
+        if (attackphase == 1 && currentRatio < ratio - 1) {
+            currentRatio *= (1 + attack);
+        }
+        if (currentRatio >= ratio - 1) {
+            attackphase = 0;
+            releasephase = 1;
+        }
+        if (releasephase == 1 && currentRatio > 0.) {
+            currentRatio *= release;
+        }
+        output = input / (1. + currentRatio);
+        return output * (1 + log(ratio));
+    }
+    double compress(double input) { return compressor(input, ratio, threshold, attack, release); }  // C:1269-1298: the same step on the members
+
+    double input = 0;
+    double ratio = 0;
+    double currentRatio = 0;
+    double threshold = 0;
+    double output = 0;
+    double attack = 0;
+    double release = 0;
+    double amplitude = 0;
+
+    // (the setters store pow(0.01, ...), which compress() then uses as 1 + attack: the reference's quirk, kept)
+    void setAttack(double attackMS) { attack = pow(0.01, 1.0 / (attackMS * maxiSettings::sampleRate * 0.001)); }
+    void setRelease(double releaseMS) { release = pow(0.01, 1.0 / (releaseMS * maxiSettings::sampleRate * 0.001)); }
+    void setThreshold(double thresholdI) { threshold = thresholdI; }
+    void setRatio(double ratioF) { ratio = ratioF; }
+    long holdtime = 0;
+    long holdcount = 0;
+    int attackphase = 0, holdphase = 0, releasephase = 0;
+};
+
+class maxiEnvelope {
+    double period = 0;
+    double output = 0;
+    double startval = 0;
+    double currentval = 0;
+    int isPlaying = 0;
+    // an index of the reference's reads, held inside the first n entries of the vector (the one departure: the reference
+    // indexes out of its vector there; its reads of segments[valindex + 2], which nothing uses, are not made)
+    static size_t at(int i, int n, const std::vector<double> &segments) {
+        if ((size_t)(n < 0 ? 0 : n) > segments.size()) n = (int)segments.size();
+        return i < 0 || n < 1 ? 0 : (size_t)(i > n - 1 ? n - 1 : i);
+    }
+
+public:
+    maxiEnvelope() {}
+    double line(int numberofsegments, std::vector<double> &segments) {  // C:377-402
+        if (isPlaying == 1) {
+            if (segments.empty()) return output = amplitude;
+            const size_t i = at(valindex, numberofsegments, segments), j = at((int)i + 1, numberofsegments, segments);
+            period = 4. / (segments[j] * 0.0044);
+            currentval = segments[i];
+            if (currentval - amplitude > 0.0000001 && valindex < numberofsegments) {
+                amplitude += ((currentval - startval) / (maxiSettings::sampleRate / period));
+            } else if (currentval - amplitude < -0.0000001 && valindex < numberofsegments) {
+                amplitude -= (((currentval - startval) * (-1)) / (maxiSettings::sampleRate / period));
+            } else if (valindex > numberofsegments - 1) {
+                valindex = numberofsegments - 2;
+            } else {
+                valindex = valindex + 2;
+                startval = currentval;
+            }
+            output = amplitude;
+        } else {
+            output = 0;
+        }
+        return (output);
+    }
+    void trigger(int index, double amp) {  // C:407-412
+        isPlaying = 1;
+        valindex = index;
+        amplitude = amp;
+    }
+    int valindex = 0;
+    double amplitude = 0;
+    void setValindex(int index) { valindex = index; }
+    void setAmplitude(double amp) { amplitude = amp; }
+    int getValindex() const { return valindex; }
+    double getAmplitude() const { return amplitude; }
+};
+
 // ---- maxiCounter (H:1953-1977), maxiIndex (H:1982-2013), maxiStep (H:2093-2141), maxiRatioSeq (H:2146-2230), maxiZXToPulse
 // (H:2235-2262): the reference's control-rate sequencing helpers, host value types like maxiTrigger -- a patch calls them once
 // per sample between its unit generators, and their outputs feed those as plain arguments.  The same arithmetic as the banks'

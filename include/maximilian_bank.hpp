@@ -1085,6 +1085,216 @@ private:
     maxigpu::DeviceArray<double> d_par_, d_st_;
 };
 
+// ---- the classic core classes: maxiDyn, maxiEnvelope, maxiLagExp<double>, maxiMap / maxiConvert (kernel K23) --------------
+// V x maxiDyn (mxg_dyn_gate_render / mxg_dyn_compress_render).  gate() and compressor() take one value per voice; compress() runs
+// the same step on the members the four setters left (setAttack / setRelease in ms store pow(0.01, ...), which compress() uses as
+// 1 + attack: the reference's quirk).  Gate and compressor share one state, as the members of one maxiDyn are.  d_out is distinct
+// from d_in.  The *_blocks overloads read a device block [N][V] for every parameter whose MXG_CLASSIC_PS_* bit is set.
+class maxiDynBank {
+public:
+    explicit maxiDynBank(size_t voices) : V(voices), ratio_(voices, 0.0), threshold_(voices, 0.0), attack_(voices, 0.0), release_(voices, 0.0) {
+        d_dst_.resize(3 * V);
+        d_ist_.resize(4 * V);
+    }
+    size_t voices() const { return V; }
+    void gate(size_t N, const double *d_in, const std::vector<double> &threshold, const std::vector<int64_t> &holdtime,
+              const std::vector<double> &attack, const std::vector<double> &release, double *d_out, void *stream = nullptr) {
+        per_voice(threshold, thr_, "gate");
+        per_voice(attack, att_, "gate");
+        per_voice(release, rel_, "gate");
+        if (holdtime.size() != V) throw std::runtime_error("maxiDynBank::gate: one value per voice");
+        hold_.upload(holdtime);
+        gate_blocks(N, d_in, thr_.get(), att_.get(), rel_.get(), 0, hold_.get(), d_out, stream);
+    }
+    void gate(size_t N, const double *d_in, double threshold, long holdtime, double attack, double release, double *d_out, void *stream = nullptr) {
+        gate(N, d_in, std::vector<double>(V, threshold), std::vector<int64_t>(V, holdtime), std::vector<double>(V, attack),
+             std::vector<double>(V, release), d_out, stream);
+    }
+    void gate_blocks(size_t N, const double *d_in, const double *d_threshold, const double *d_attack, const double *d_release, int ps_flags,
+                     const int64_t *d_holdtime, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_dyn_gate_render(V, N, d_in, d_threshold, d_attack, d_release, ps_flags, d_holdtime, d_dst_.get(), d_ist_.get(), d_out,
+                                           stream), "mxg_dyn_gate_render");
+    }
+    void compressor(size_t N, const double *d_in, const std::vector<double> &ratio, const std::vector<double> &threshold,
+                    const std::vector<double> &attack, const std::vector<double> &release, double *d_out, void *stream = nullptr) {
+        per_voice(ratio, rat_, "compressor");
+        per_voice(threshold, thr_, "compressor");
+        per_voice(attack, att_, "compressor");
+        per_voice(release, rel_, "compressor");
+        std::vector<double> mk(V);
+        for (size_t v = 0; v < V; v++) mk[v] = mxg_dyn_makeup_host(ratio[v]);  // 1 + log(ratio), host libm
+        mk_.upload(mk);
+        compressor_blocks(N, d_in, rat_.get(), mk_.get(), thr_.get(), att_.get(), rel_.get(), 0, d_out, stream);
+    }
+    void compressor(size_t N, const double *d_in, double ratio, double threshold, double attack, double release, double *d_out, void *stream = nullptr) {
+        compressor(N, d_in, std::vector<double>(V, ratio), std::vector<double>(V, threshold), std::vector<double>(V, attack),
+                   std::vector<double>(V, release), d_out, stream);
+    }
+    // d_makeup: mxg_dyn_makeup_host of every ratio, in the layout of d_ratio
+    void compressor_blocks(size_t N, const double *d_in, const double *d_ratio, const double *d_makeup, const double *d_threshold,
+                           const double *d_attack, const double *d_release, int ps_flags, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_dyn_compress_render(V, N, d_in, d_ratio, d_makeup, d_threshold, d_attack, d_release, ps_flags, d_dst_.get(),
+                                               d_ist_.get(), d_out, stream), "mxg_dyn_compress_render");
+    }
+    void compress(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        compressor(N, d_in, ratio_, threshold_, attack_, release_, d_out, stream);
+    }
+    void setAttack(double attackMS) { attack_.assign(V, mxg_dyn_coeff_host(attackMS, (double)maxiSettings::sampleRate)); }
+    void setRelease(double releaseMS) { release_.assign(V, mxg_dyn_coeff_host(releaseMS, (double)maxiSettings::sampleRate)); }
+    void setThreshold(double thresholdI) { threshold_.assign(V, thresholdI); }
+    void setRatio(double ratioF) { ratio_.assign(V, ratioF); }
+    // state arrays on the device (include/maxigpu.h): double [3][V] and int64 [4][V]
+    double *state() { return d_dst_.get(); }
+    int64_t *phases() { return d_ist_.get(); }
+
+private:
+    void per_voice(const std::vector<double> &p, maxigpu::DeviceArray<double> &d, const char *what) {
+        if (p.size() != V) throw std::runtime_error(std::string("maxiDynBank::") + what + ": one value per voice");
+        maxigpu::check(mxg_sync(), "mxg_sync");  // (an earlier render may still read the last values)
+        d.upload(p);
+    }
+    size_t V;
+    std::vector<double> ratio_, threshold_, attack_, release_;
+    maxigpu::DeviceArray<double> thr_, att_, rel_, rat_, mk_, d_dst_;
+    maxigpu::DeviceArray<int64_t> hold_, d_ist_;
+};
+
+// V x maxiEnvelope (mxg_envelope_line_render).  segments: one table (value, time, value, time ...) for every voice, or [S][V] with
+// a count per voice.  trigger() acts between two blocks; line(N, d_trig, ...) reads a trigger block [N][V] whose non-zero values
+// perform trigger(index, amp) before that sample.  A trigger index outside [0, count - 2] is refused.
+class maxiEnvelopeBank {
+public:
+    maxiEnvelopeBank(size_t voices, const std::vector<double> &segments) : V(voices), S(segments.size()) {
+        std::vector<double> sv(S * V);
+        for (size_t s = 0; s < S; s++)
+            for (size_t v = 0; v < V; v++) sv[s * V + v] = segments[s];
+        init(sv, std::vector<int32_t>(V, (int32_t)S));
+    }
+    maxiEnvelopeBank(size_t voices, size_t entries, const std::vector<double> &segments_sv, const std::vector<int32_t> &count) : V(voices), S(entries) {
+        init(segments_sv, count);
+    }
+    size_t voices() const { return V; }
+    void trigger(const std::vector<int32_t> &index, const std::vector<double> &amp, const std::vector<int32_t> *mask = nullptr) {
+        if (index.size() != V || amp.size() != V || (mask && mask->size() != V)) throw std::runtime_error("maxiEnvelopeBank::trigger: one value per voice");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        std::vector<double> dst = d_dst_.download();
+        std::vector<int32_t> ist = d_ist_.download();
+        maxigpu::check(mxg_envelope_trigger_host(V, index.data(), amp.data(), mask ? mask->data() : nullptr, count_.data(), dst.data(), ist.data()),
+                       "mxg_envelope_trigger_host");
+        d_dst_.upload(dst);
+        d_ist_.upload(ist);
+    }
+    void trigger(int index, double amp) { trigger(std::vector<int32_t>(V, index), std::vector<double>(V, amp)); }
+    void line(size_t N, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_envelope_line_render(V, N, S, d_seg_.get(), d_count_.get(), nullptr, nullptr, nullptr, d_dst_.get(), d_ist_.get(), d_out,
+                                                stream), "mxg_envelope_line_render");
+    }
+    void line(size_t N, const double *d_trig, int trig_index, double trig_amp, double *d_out, void *stream = nullptr) {
+        for (size_t v = 0; v < V; v++)
+            if (trig_index < 0 || trig_index > count_[v] - 2) throw std::runtime_error("maxiEnvelopeBank::line: trigger index outside [0, count - 2]");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_tix_.upload(std::vector<int32_t>(V, trig_index));
+        d_tamp_.upload(std::vector<double>(V, trig_amp));
+        maxigpu::check(mxg_envelope_line_render(V, N, S, d_seg_.get(), d_count_.get(), d_trig, d_tix_.get(), d_tamp_.get(), d_dst_.get(), d_ist_.get(),
+                                                d_out, stream), "mxg_envelope_line_render");
+    }
+    // state arrays on the device (include/maxigpu.h): double [2][V] = amplitude, startval; int32 [2][V] = valindex, isPlaying
+    double *state() { return d_dst_.get(); }
+    int32_t *indices() { return d_ist_.get(); }
+
+private:
+    void init(const std::vector<double> &sv, const std::vector<int32_t> &count) {
+        if (S < 2 || S > MXG_ENVELOPE_MAX_S || sv.size() != S * V || count.size() != V) throw std::runtime_error("maxiEnvelopeBank: 2 .. 64 entries, [S][V], one count per voice");
+        for (int32_t c : count)
+            if (c < 2 || (size_t)c > S) throw std::runtime_error("maxiEnvelopeBank: a count outside 2 .. S");
+        count_ = count;
+        d_seg_.upload(sv);
+        d_count_.upload(count);
+        d_dst_.resize(2 * V);
+        d_ist_.resize(2 * V);
+    }
+    size_t V, S;
+    std::vector<int32_t> count_;
+    maxigpu::DeviceArray<double> d_seg_, d_dst_, d_tamp_;
+    maxigpu::DeviceArray<int32_t> d_count_, d_ist_, d_tix_;
+};
+
+// V x maxiLagExp<double> (mxg_lag_render): val = (alpha * x) + (alphaReciprocal * val) over a block; alpha and alphaReciprocal are
+// independent, as in the reference (init sets both, setAlpha only alpha).  d_out is distinct from d_in.
+class maxiLagExpBank {
+public:
+    maxiLagExpBank(size_t voices, double alpha = 0.5, double val = 0.0) : V(voices) { init(alpha, val); }
+    size_t voices() const { return V; }
+    void init(double alpha, double val) {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_alpha_.upload(std::vector<double>(V, alpha));
+        d_recip_.upload(std::vector<double>(V, 1.0 - alpha));
+        d_val_.upload(std::vector<double>(V, val));
+    }
+    void setAlpha(double alpha) { maxigpu::check(mxg_sync(), "mxg_sync"); d_alpha_.upload(std::vector<double>(V, alpha)); }
+    void setAlphaReciprocal(double r) { maxigpu::check(mxg_sync(), "mxg_sync"); d_recip_.upload(std::vector<double>(V, r)); }
+    void setVal(double val) { maxigpu::check(mxg_sync(), "mxg_sync"); d_val_.upload(std::vector<double>(V, val)); }
+    void addSample(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_lag_render(V, N, d_in, d_alpha_.get(), d_recip_.get(), 0, d_val_.get(), d_out, stream), "mxg_lag_render");
+    }
+    void addSample(size_t N, const double *d_in, const double *d_alpha, const double *d_alpha_reciprocal, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_lag_render(V, N, d_in, d_alpha, d_alpha_reciprocal, 1, d_val_.get(), d_out, stream), "mxg_lag_render");
+    }
+    std::vector<double> value() const {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        return d_val_.download();
+    }
+
+private:
+    size_t V;
+    maxigpu::DeviceArray<double> d_alpha_, d_recip_, d_val_;
+};
+
+// V x maxiMap / maxiConvert (mxg_map_render): stateless, flat over the block; d_out may be d_in.  Ranges are one value for the
+// bank or one per voice.  linlin and clamp are the reference's bits; the other four use the device's pow / log / log10.
+class maxiMapBank {
+public:
+    explicit maxiMapBank(size_t voices) : V(voices) {}
+    size_t voices() const { return V; }
+    void linlin(size_t N, const double *d_in, double inMin, double inMax, double outMin, double outMax, double *d_out, void *stream = nullptr) {
+        ranged(MXG_MAP_LINLIN, N, d_in, spread(inMin, inMax, outMin, outMax), d_out, stream);
+    }
+    void linexp(size_t N, const double *d_in, double inMin, double inMax, double outMin, double outMax, double *d_out, void *stream = nullptr) {
+        ranged(MXG_MAP_LINEXP, N, d_in, spread(inMin, inMax, outMin, outMax), d_out, stream);
+    }
+    void explin(size_t N, const double *d_in, double inMin, double inMax, double outMin, double outMax, double *d_out, void *stream = nullptr) {
+        ranged(MXG_MAP_EXPLIN, N, d_in, spread(inMin, inMax, outMin, outMax), d_out, stream);
+    }
+    void clamp(size_t N, const double *d_in, double low, double high, double *d_out, void *stream = nullptr) {
+        ranged(MXG_MAP_CLAMP, N, d_in, spread(low, high, 0.0, 0.0), d_out, stream);
+    }
+    // range4v: [4][V] = inMin, inMax, outMin, outMax per voice
+    void ranged(int mode, size_t N, const double *d_in, const std::vector<double> &range4v, double *d_out, void *stream = nullptr) {
+        if (range4v.size() != 4 * V) throw std::runtime_error("maxiMapBank: a range is [4][V]");
+        std::vector<double> aux(V);
+        maxigpu::check(mxg_map_range_host(mode, V, range4v.data(), aux.data()), "mxg_map_range_host");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_range_.upload(range4v);
+        d_aux_.upload(aux);
+        maxigpu::check(mxg_map_render(mode, V, N, d_in, d_range_.get(), d_aux_.get(), d_out, stream), "mxg_map_render");
+    }
+    void ampToDbs(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_map_render(MXG_MAP_AMPTODBS, V, N, d_in, nullptr, nullptr, d_out, stream), "mxg_map_render");
+    }
+    void dbsToAmp(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_map_render(MXG_MAP_DBSTOAMP, V, N, d_in, nullptr, nullptr, d_out, stream), "mxg_map_render");
+    }
+
+private:
+    std::vector<double> spread(double a, double b, double c, double d) const {
+        std::vector<double> r(4 * V);
+        for (size_t v = 0; v < V; v++) { r[v] = a; r[V + v] = b; r[2 * V + v] = c; r[3 * V + v] = d; }
+        return r;
+    }
+    size_t V;
+    maxigpu::DeviceArray<double> d_range_, d_aux_;
+};
+
 // V x maxiPolyBLEP (mxg_polyblep_render, K20): one waveform for the bank, a pulse width and a phase per voice, the phase carried
 // from call to call.  set_waveform / set_pulse_width / sync act between two blocks, as the reference's setters do between two
 // samples.  render(N, d_freq, per_sample, ...) reads one frequency per voice [V] or a block [N][V].

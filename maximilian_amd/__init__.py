@@ -13,6 +13,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     dattaro_layout, maxiSeqBank, maxiTriggerBank, maxiCounterBank, maxiStepBank, maxiIndexBank,
                     maxiZXToPulseBank, seq_table, seq_ratio_tables, maxiAnalysisBank, maxiKuramotoBank, envfollow_coeff, analysis_want, OSC_WAVEFORMS,
                     maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
+                    maxiDynBank, maxiEnvelopeBank, maxiLagExpBank, maxiMapBank, dyn_coeff, dyn_makeup, MAP_MODES, CLASSIC_PS,
                     maxiPolyBLEPBank, polyblep_sync, POLYBLEP_WAVEFORMS,
                     maxiKickBank, maxiSnareBank, maxiHatsBank, maxiClockBank, DRUM_KINDS,
                     maxiAtomBank, ATOM_KINDS, ATOM_ONSETS,

@@ -130,6 +130,20 @@ SIGNATURES = {
     "mxg_select_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mxg_line_prepare_host": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "mxg_line_render": (c_int, [c_size_t, c_size_t, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_dyn_coeff_host": (c_double, [c_double, c_double]),
+    "mxg_dyn_makeup_host": (c_double, [c_double]),
+    "mxg_dyn_gate_render": (c_int, [c_size_t, c_size_t] + [c_void_p] * 4 + [c_int] + [c_void_p] * 5),
+    "mxg_dyn_gate_host": (c_int, [c_size_t, c_size_t] + [c_void_p] * 4 + [c_int] + [c_void_p] * 4),
+    "mxg_dyn_compress_render": (c_int, [c_size_t, c_size_t] + [c_void_p] * 6 + [c_int] + [c_void_p] * 4),
+    "mxg_dyn_compress_host": (c_int, [c_size_t, c_size_t] + [c_void_p] * 6 + [c_int] + [c_void_p] * 3),
+    "mxg_envelope_trigger_host": (c_int, [c_size_t] + [c_void_p] * 6),
+    "mxg_envelope_line_render": (c_int, [c_size_t, c_size_t, c_size_t] + [c_void_p] * 9),
+    "mxg_envelope_line_host": (c_int, [c_size_t, c_size_t, c_size_t] + [c_void_p] * 8),
+    "mxg_lag_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mxg_lag_host": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mxg_map_range_host": (c_int, [c_int, c_size_t, c_void_p, c_void_p]),
+    "mxg_map_render": (c_int, [c_int, c_size_t, c_size_t] + [c_void_p] * 5),
+    "mxg_map_host": (c_int, [c_int, c_size_t, c_size_t] + [c_void_p] * 4),
     "mxg_polyblep_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "mxg_polyblep_host": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     "mxg_drum_render": (c_int, [c_int, c_int, c_size_t, c_size_t, c_void_p, c_int] + [c_void_p] * 13),

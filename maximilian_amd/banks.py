@@ -1381,6 +1381,237 @@ class maxiLineBank(_Bank):
         return out
 
 
+MAP_MODES = {"linlin": 0, "linexp": 1, "explin": 2, "clamp": 3, "ampToDbs": 4, "dbsToAmp": 5}  # MXG_MAP_* (include/maxigpu.h)
+CLASSIC_PS = {"threshold": 1, "attack": 2, "release": 4, "ratio": 8}                          # MXG_CLASSIC_PS_*
+ENVELOPE_MAX_S = 64
+
+
+def dyn_coeff(ms, sample_rate=None):
+    """maxiDyn::setAttack / setRelease: pow(0.01, 1.0 / (ms * sampleRate * 0.001)) with the host libm (mxg_dyn_coeff_host)."""
+    return lib().mxg_dyn_coeff_host(float(ms), float(maxiSettings.sampleRate if sample_rate is None else sample_rate))
+
+
+def dyn_makeup(ratio):
+    """1 + log(ratio) with the host libm (mxg_dyn_makeup_host): the compressor's make-up factor; scalar / array alike."""
+    f = lib().mxg_dyn_makeup_host
+    return np.array([f(float(r)) for r in np.atleast_1d(np.asarray(ratio, np.float64)).reshape(-1)]).reshape(np.shape(ratio))
+
+
+class maxiDynBank(_Bank):
+    """V x maxiDyn (src/maximilian.cpp:1200-1314; mxg_dyn_gate_render / mxg_dyn_compress_render, K23).  gate() and compressor()
+    take the reference's arguments: scalar / [V], or a device or host [N][V] block (one value per sample); compress() runs the
+    same step on the members the four setters left (setAttack / setRelease in ms: the stored value is pow(0.01, ...), which
+    compress() uses as 1 + attack -- the reference's quirk).  State: dst [3][V] = amplitude, currentRatio, output; ist int64
+    [4][V] = holdcount, attackphase, holdphase, releasephase; gate and compressor share it, as the members of one maxiDyn are.
+    Bit-exact, the state included; out is distinct from x."""
+
+    def __init__(self, voices, stream=None):
+        super().__init__(voices, stream)
+        self.dst = DeviceBuffer((3, self.V))
+        self.ist = DeviceBuffer((4, self.V), np.int64)
+        self.ratio, self.threshold, self.attack, self.release = (np.zeros(self.V) for _ in range(4))
+
+    def _params(self, N, **named):
+        ptrs, flags = [], 0
+        for name, x in named.items():
+            p, ps = _fx_param(x, self.V, N, np.float64, name)
+            ptrs.append(p)
+            flags |= CLASSIC_PS[name] * ps
+        return ptrs, flags
+
+    def gate(self, x, threshold=0.9, holdtime=1, attack=1, release=0.9995, out=None):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        (thr, att, rel), flags = self._params(N, threshold=threshold, attack=attack, release=release)
+        hold = _as_dev(holdtime, self.V, np.int64)
+        out = self._out(N, out)
+        check(lib().mxg_dyn_gate_render(self.V, N, _ptr(x), _ptr(thr), _ptr(att), _ptr(rel), flags, _ptr(hold), self.dst.ptr, self.ist.ptr,
+                                        _ptr(out), self.stream), "mxg_dyn_gate_render")
+        return out
+
+    def compressor(self, x, ratio, threshold=0.9, attack=1, release=0.9995, out=None, makeup=None):
+        """makeup: the make-up factors 1 + log(ratio) of `ratio`, in its layout (dyn_makeup: the host libm's, as in the reference).
+        None: they are formed here from a host ratio.  A ratio that lives on the device comes with its make-up block, which its
+        producer formed once on the host; nothing is then copied back."""
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        on_device = isinstance(ratio, DeviceBuffer) or hasattr(ratio, "data_ptr")
+        if on_device and makeup is None:
+            raise ValueError("ratio: a device-resident ratio needs makeup= (dyn_makeup of the same values, in the same layout)")
+        (thr, att, rel, rat), flags = self._params(N, threshold=threshold, attack=attack, release=release, ratio=ratio)
+        if makeup is None:
+            makeup = dyn_makeup(np.asarray(ratio, np.float64))
+        mk, mk_ps = _fx_param(makeup, self.V, N, np.float64, "makeup")
+        if mk_ps != (1 if flags & CLASSIC_PS["ratio"] else 0):
+            raise ValueError("makeup: ratio and makeup travel together, both [V] or both [N][V]")
+        out = self._out(N, out)
+        check(lib().mxg_dyn_compress_render(self.V, N, _ptr(x), _ptr(rat), _ptr(mk), _ptr(thr), _ptr(att), _ptr(rel), flags, self.dst.ptr,
+                                            self.ist.ptr, _ptr(out), self.stream), "mxg_dyn_compress_render")
+        return out
+
+    def compress(self, x, out=None):
+        return self.compressor(x, self.ratio, self.threshold, self.attack, self.release, out=out)
+
+    def _set(self, name, value):
+        setattr(self, name, np.ascontiguousarray(np.broadcast_to(np.asarray(value, np.float64), (self.V,))))
+
+    def setAttack(self, attackMS):
+        self._set("attack", [dyn_coeff(ms) for ms in np.broadcast_to(np.asarray(attackMS, np.float64), (self.V,))])
+
+    def setRelease(self, releaseMS):
+        self._set("release", [dyn_coeff(ms) for ms in np.broadcast_to(np.asarray(releaseMS, np.float64), (self.V,))])
+
+    def setThreshold(self, thresholdI):
+        self._set("threshold", thresholdI)
+
+    def setRatio(self, ratioF):
+        self._set("ratio", ratioF)
+
+
+class maxiEnvelopeBank(_Bank):
+    """V x maxiEnvelope (src/maximilian.cpp:377-412; mxg_envelope_line_render, K23).  segments: one table for every voice ([S]) or
+    a table per voice ([S][V], `count` entries of voice v in use): value, time, value, time ...  State: dst [2][V] = amplitude,
+    startval; ist int32 [2][V] = valindex, isPlaying.  trigger() between blocks writes the state; a device trigger block in
+    line() performs trigger(trig_index, trig_amp) before the samples where it is non-zero.  Bit-exact, the state included.  A
+    trigger index outside [0, count - 2] is refused (the reference indexes out of its vector there)."""
+
+    def __init__(self, voices, segments, count=None, stream=None):
+        super().__init__(voices, stream)
+        seg = np.asarray(segments, np.float64)
+        if seg.ndim == 1:
+            seg = np.repeat(seg[:, None], self.V, axis=1)
+        self.S = seg.shape[0]
+        if not 2 <= self.S <= ENVELOPE_MAX_S or seg.shape != (self.S, self.V):
+            raise ValueError("segments: [S] or [S][V] with S in 2 .. %d, got %s" % (ENVELOPE_MAX_S, seg.shape))
+        self._count = np.ascontiguousarray(np.broadcast_to(np.asarray(self.S if count is None else count, np.int32), (self.V,)))
+        if (self._count < 2).any() or (self._count > self.S).any():
+            raise ValueError("count: 2 .. S entries per voice")
+        self.segments = DeviceBuffer.from_numpy(seg)
+        self.count = DeviceBuffer.from_numpy(self._count)
+        self.dst = DeviceBuffer((2, self.V))
+        self.ist = DeviceBuffer((2, self.V), np.int32)
+        self.trig_index = DeviceBuffer(self.V, np.int32)
+        self.trig_amp = DeviceBuffer(self.V)
+
+    def trigger(self, index, amp, voices=None):
+        """maxiEnvelope::trigger(index, amp) on every voice, or on `voices` (indices); arguments scalar or [V]."""
+        V = self.V
+        dst, ist = self.dst.numpy(), self.ist.numpy()
+        ix = np.ascontiguousarray(np.broadcast_to(np.asarray(index, np.int32), (V,)))
+        am = np.ascontiguousarray(np.broadcast_to(np.asarray(amp, np.float64), (V,)))
+        mask = None
+        if voices is not None:
+            mask = np.zeros(V, np.int32)
+            mask[np.atleast_1d(np.asarray(voices, np.int64))] = 1
+        check(lib().mxg_envelope_trigger_host(V, ix.ctypes.data, am.ctypes.data, None if mask is None else mask.ctypes.data,
+                                              self._count.ctypes.data, dst.ctypes.data, ist.ctypes.data), "mxg_envelope_trigger_host")
+        self.dst.upload(dst)
+        self.ist.upload(ist)
+
+    def line(self, N=None, trigger=None, trig_index=0, trig_amp=0.0, out=None):
+        """N samples of line(); trigger: a device [N][V] block whose non-zero values trigger (trig_index, trig_amp: scalar / [V])."""
+        if trigger is not None:
+            N = trigger.shape[0]
+            _fx_dev(trigger, np.float64, "trigger", (N * self.V,))
+            ix = np.ascontiguousarray(np.broadcast_to(np.asarray(trig_index, np.int32), (self.V,)))
+            if (ix < 0).any() or (ix > self._count - 2).any():
+                raise ValueError("trig_index: outside [0, count - 2]")
+            self.trig_index.upload(ix)
+            self.trig_amp.upload(np.broadcast_to(np.asarray(trig_amp, np.float64), (self.V,)))
+        elif N is None:
+            raise ValueError("N: without a trigger block the number of samples is needed")
+        out = self._out(int(N), out)
+        check(lib().mxg_envelope_line_render(self.V, int(N), self.S, self.segments.ptr, self.count.ptr, _ptr(trigger), self.trig_index.ptr,
+                                             self.trig_amp.ptr, self.dst.ptr, self.ist.ptr, _ptr(out), self.stream), "mxg_envelope_line_render")
+        return out
+
+    @property
+    def valindex(self):
+        return self.ist.numpy()[0]
+
+    @property
+    def amplitude(self):
+        return self.dst.numpy()[0]
+
+
+class maxiLagExpBank(_Bank):
+    """V x maxiLagExp<double> (H:499-560; mxg_lag_render, K23): val = (alpha * x) + (alphaReciprocal * val) over a block.
+    alpha and alphaReciprocal are independent, as in the reference: init() sets both, setAlpha() only alpha.  Bit-exact."""
+
+    def __init__(self, voices, alpha=0.5, val=0.0, stream=None):
+        super().__init__(voices, stream)
+        self.init(alpha, val)
+
+    def init(self, alpha, val):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, np.float64), (self.V,)))
+        self.alpha, self.alphaReciprocal = DeviceBuffer.from_numpy(a), DeviceBuffer.from_numpy(1.0 - a)
+        self.val = DeviceBuffer.from_numpy(np.broadcast_to(np.asarray(val, np.float64), (self.V,)))
+
+    def setAlpha(self, alpha):
+        self.alpha.upload(np.broadcast_to(np.asarray(alpha, np.float64), (self.V,)))
+
+    def setAlphaReciprocal(self, alphaReciprocal):
+        self.alphaReciprocal.upload(np.broadcast_to(np.asarray(alphaReciprocal, np.float64), (self.V,)))
+
+    def setVal(self, val):
+        self.val.upload(np.broadcast_to(np.asarray(val, np.float64), (self.V,)))
+
+    def addSample(self, x, alpha=None, alphaReciprocal=None, out=None):
+        """A block [N][V] of samples -> the value after each; alpha / alphaReciprocal: device [N][V] blocks for a pair per sample."""
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        a, r, ps = self.alpha, self.alphaReciprocal, 0
+        if alpha is not None:
+            _fx_dev(alpha, np.float64, "alpha", (N * self.V,))
+            _fx_dev(alphaReciprocal, np.float64, "alphaReciprocal", (N * self.V,))
+            a, r, ps = alpha, alphaReciprocal, 1
+        out = self._out(N, out)
+        check(lib().mxg_lag_render(self.V, N, _ptr(x), _ptr(a), _ptr(r), ps, self.val.ptr, _ptr(out), self.stream), "mxg_lag_render")
+        return out
+
+    def value(self):
+        return self.val.numpy()
+
+
+class maxiMapBank(_Bank):
+    """V x maxiMap / maxiConvert over one block [N][V] (H:801-854, 955-961; mxg_map_render, K23).  Ranges are scalar / [V].  out
+    may be x (in place).  linlin and clamp are the reference's bits; linexp, explin, ampToDbs and dbsToAmp use the device's pow /
+    log / log10 (tolerance); explin's log(inMax / inMin) comes from the host libm."""
+
+    def _render(self, mode, x, rng=(), out=None):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        dr = da = None
+        if rng:
+            r = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(t, np.float64), (self.V,)) for t in rng]))
+            dr = DeviceBuffer.from_numpy(r)
+            if mode == "explin":
+                aux = np.zeros(self.V)
+                check(lib().mxg_map_range_host(MAP_MODES[mode], self.V, r.ctypes.data, aux.ctypes.data), "mxg_map_range_host")
+                da = DeviceBuffer.from_numpy(aux)
+        out = self._out(N, out)
+        check(lib().mxg_map_render(MAP_MODES[mode], self.V, N, _ptr(x), _ptr(dr), _ptr(da), _ptr(out), self.stream), "mxg_map_render")
+        return out
+
+    def linlin(self, x, inMin, inMax, outMin, outMax, out=None):
+        return self._render("linlin", x, (inMin, inMax, outMin, outMax), out)
+
+    def linexp(self, x, inMin, inMax, outMin, outMax, out=None):
+        return self._render("linexp", x, (inMin, inMax, outMin, outMax), out)
+
+    def explin(self, x, inMin, inMax, outMin, outMax, out=None):
+        return self._render("explin", x, (inMin, inMax, outMin, outMax), out)
+
+    def clamp(self, x, low, high, out=None):
+        return self._render("clamp", x, (low, high), out)
+
+    def ampToDbs(self, x, out=None):
+        return self._render("ampToDbs", x, (), out)
+
+    def dbsToAmp(self, x, out=None):
+        return self._render("dbsToAmp", x, (), out)
+
+
 POLYBLEP_WAVEFORMS = {"SINE": 0, "COSINE": 1, "TRIANGLE": 2, "SQUARE": 3, "RECTANGLE": 4, "SAWTOOTH": 5, "RAMP": 6, "MODIFIED_TRIANGLE": 7,
                       "MODIFIED_SQUARE": 8, "HALF_WAVE_RECTIFIED_SINE": 9, "FULL_WAVE_RECTIFIED_SINE": 10, "TRIANGULAR_PULSE": 11,
                       "TRAPEZOID_FIXED": 12, "TRAPEZOID_VARIABLE": 13}

@@ -13,56 +13,16 @@
 //
 // line_kernel is a state machine and takes the streaming shape of mxg_stream.h: one lane = one voice, chunks of 8 samples, surplus lanes shadow
 // the last voice (pair) and store no state, whole chunks leave through emit_chunk, the trigger is requested a chunk ahead.
-// No scratch in any instantiation.
+// No scratch in any instantiation.  The flat skeleton is mxg_flat.h.
 #include <math.h>
 
 #include "mxg_common.h"
+#include "mxg_flat.h"
 #include "mxg_stream.h"
 #include "mxg_shaper.h"
 
 namespace mxg {
 namespace {
-
-constexpr int kFlatBlock = 256;  // threads of a flat workgroup
-constexpr int kFlatUnits = 4;    // units per thread
-
-struct FlatGeom {
-    size_t E, V;
-    unsigned stride_mod;  // (kFlatBlock * elements per unit) % V
-    int st;               // store flavour of the 16-byte units: 1 / 2 / 3 = plain / write-through / non-temporal (emit_chunk's numbering)
-};
-
-__device__ __forceinline__ void flat_store2(double *p, double a, double b, int st) {
-    if (st == 2) store2<2>(p, a, b);
-    else if (st == 3) store2<1>(p, a, b);
-    else store2<0>(p, a, b);
-}
-
-// element % V for the first element of a thread's first unit
-__device__ __forceinline__ size_t flat_voice0(size_t e, size_t V) {
-    if (V <= 0xffffffffu && e <= 0xffffffffu) return (uint32_t)e % (uint32_t)V;
-    return e % V;
-}
-__device__ __forceinline__ size_t flat_next(size_t m, size_t step, size_t V) {
-    m += step;
-    return m >= V ? m - V : m;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void flat_load(const double *p, size_t e, double (&x)[VEC ? 2 : 1]) {
-    if constexpr (VEC) {
-        const double2v r = *reinterpret_cast<const double2v *>(p + e);
-        x[0] = r.x;
-        x[1] = r.y;
-    } else {
-        x[0] = p[e];
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void flat_store(double *p, size_t e, const double (&y)[VEC ? 2 : 1], int st) {
-    if constexpr (VEC) flat_store2(p + e, y[0], y[1], st);
-    else p[e] = y[0];
-}
 
 // ---- maxiNonlinearity ------------------------------------------------------------------------------------------------
 struct ShapeArgs {
@@ -302,22 +262,6 @@ __global__ void __launch_bounds__(256) line_kernel(LineArgs A, const double *__r
     A.st[V + v] = S.last;
     A.st[2 * V + v] = S.triggered;
     A.st[3 * V + v] = S.complete ? 1.0 : 0.0;
-}
-
-// the flavour of a flat launch: 16-byte units where every pointer allows it (`all` = the OR of their addresses) and the knob
-// rw_store is not 1 (the 8-byte stores); blocks from 64 MB take the write-through stores (mxg_common.h, rw_store_choice)
-FlatGeom flat_geom(size_t V, size_t N, uintptr_t all, bool *vec) {
-    const size_t E = V * N;
-    int rw = tune_get("rw_store");
-    if (rw == 0) rw = E * sizeof(double) >= ((size_t)64 << 20) ? 3 : 2;
-    *vec = rw >= 2 && !(all & 15);
-    const size_t stride = (size_t)kFlatBlock * (*vec ? 2 : 1);
-    return {E, V, (unsigned)(stride % V), *vec ? rw - 1 : 0};
-}
-unsigned flat_grid(const FlatGeom &g, bool vec) {
-    const size_t units = vec ? g.E >> 1 : g.E, per = (size_t)kFlatBlock * kFlatUnits;
-    const size_t blocks = (units + per - 1) / per;
-    return (unsigned)(blocks ? blocks : 1);  // (E == 1 in 16-byte units: the block that takes the odd element)
 }
 
 template <int MODE>
