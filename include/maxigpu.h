@@ -1142,6 +1142,44 @@ int mxg_convolve_reset(mxg_convolve *c);
 int mxg_convolve_output(mxg_convolve *c, float *d_out, int mode, void *stream);
 int mxg_convolve_input(mxg_convolve *c, const float *d_in, void *stream);
 
+/* ---- maxiConvolveBank: V independent maxiConvolve objects over I shared impulses (kernel K24) ------------ */
+/* Stream v is, bit for bit, an mxg_convolve created from impulse h_imp_of[v] and fed stream v's input -- outputs and carried
+ * state, for any split of the samples into calls and for both modes.  h_amps [I] = pointers to the impulses' amplitudes, h_lens [I]
+ * their lengths, h_pos0 [I] their play heads (each as mxg_convolve_create takes one; 1 <= I <= V), h_imp_of [V] the impulse of each
+ * stream; one fftsize / hopsize for the bank.  Every impulse is analysed exactly as mxg_convolve_create analyses it (the play-head
+ * walk, the zero padding, the division by the largest positive real / imaginary value, a zero maximum included); the frame counts
+ * K_i may differ and may be 0, and a stream's sum runs over k < K_i exactly (no zero frames stand in: 0 x Inf would differ).
+ * Bad arguments are refused, with a message that names the argument, before any device call.
+ * State per stream: its input spectra in a ring of max K_i - 1 + 16 rows -- the new rows enter it inside the multiply-accumulate
+ * kernel, so keeping the history costs nblocks rows of writes per call and no copies -- and the pending sums, from which output
+ * block 0 of the next call is transformed.  maxiIFFT's hop buffer is NOT state of the bank: maxiConvolve sets its maxiIFFT up with
+ * hop = fftsize, so a frame never reaches into the next one and the buffer is never read back. */
+typedef struct mxg_convolve_bank mxg_convolve_bank;
+mxg_convolve_bank *mxg_convolve_bank_create(size_t V, size_t I, const double *const *h_amps, const size_t *h_lens, const double *h_pos0,
+                                            const int *h_imp_of, int fftsize, int hopsize);
+int mxg_convolve_bank_destroy(mxg_convolve_bank *b);
+int mxg_convolve_bank_reset(mxg_convolve_bank *b);
+int mxg_convolve_bank_frames(const mxg_convolve_bank *b, size_t i); /* K_i */
+/* the normalised spectra of impulse i, [K_i][bins]; either pointer may be NULL */
+int mxg_convolve_bank_impulse(const mxg_convolve_bank *b, size_t i, float *h_real, float *h_imag);
+/* play(w) for nblocks * fftsize consecutive samples of every stream: d_in, d_out float [V][nblocks * fftsize] (device); mode as
+ * mxg_convolve_play.  One forward batch over all V * nblocks frames, the multiply-accumulate kernel (one launch per 16 blocks, each
+ * followed by a one-lane launch that advances the ring's head on the device), one inverse batch: the number of launches does not
+ * depend on V. */
+int mxg_convolve_bank_play(mxg_convolve_bank *b, const float *d_in, size_t nblocks, float *d_out, int mode, void *stream);
+/* the same call on the layout the other banks speak: doubles [N][V], N = nblocks * fftsize.  The input is narrowed with a plain
+ * (float) cast, as play(float w) narrows a double argument; the output is widened exactly. */
+int mxg_convolve_bank_play_nv(mxg_convolve_bank *b, const double *d_in, size_t nblocks, double *d_out, int mode, void *stream);
+/* The multiply-accumulate of a call on host arrays, no device needed: the text of the kernel's lanes (csrc/mxg_convolve.h) run in
+ * the chunks, tiles and lanes of the launches.  h_K [V] = frames of each stream's impulse, h_imp_row [V] = its first row in
+ * h_impR / h_impI [rows][bins]; h_ringR / h_ringI [V][R][bins] and *h_head (the slot the next frame takes; R >= max K, R >= 1) and
+ * h_pendR / h_pendI [V][bins] are the state, in / out; h_XR / h_XI [V][nblocks][bins] = the spectra of the new frames;
+ * h_SR / h_SI [V][nblocks][bins] receive the rows the inverse transform takes: row 0 = the pending sums on entry, row b = the sums
+ * of frame b - 1.  A lane owns 2 bins of 4 consecutive frames; a launch covers at most R - max(max K, 1) + 1 frames. */
+int mxg_convolve_bank_mac_host(size_t V, int bins, int R, const int *h_K, const int *h_imp_row, const float *h_impR, const float *h_impI,
+                               float *h_ringR, float *h_ringI, int *h_head, float *h_pendR, float *h_pendI, const float *h_XR,
+                               const float *h_XI, size_t nblocks, float *h_SR, float *h_SI);
+
 /* ---- maxiMFCC batch --------------------------------------------------------------------- */
 /* maxiMFCC::setup(numBins, numFilters, numCoeffs, minFreq, maxFreq) (L/maxiMFCC.h:56-75): builds
  * the mel filterbank and DCT tables on the host libm.  Works without a device (tables only). */

@@ -1994,6 +1994,47 @@ private:
     int fftsize_ = 0;
 };
 
+// ---- maxiConvolveBank: V maxiConvolve objects over shared impulses (include/maxigpu.h, mxg_convolve_bank_*; kernel K24) ----------
+// impulses[i] = the amplitudes of impulse i (its play head where load() leaves it: at its size), imp_of[v] = the impulse of stream v.
+// play(): float [V][nblocks * fftsize] in and out; play_nv(): the other banks' double [N][V] blocks, N = nblocks * fftsize (an
+// oscillator bank's output goes in, a maxiMixBank takes what comes out).  Stream v is bit for bit a maxiConvolveBlock of its own.
+class maxiConvolveBank {
+public:
+    maxiConvolveBank(size_t V, const std::vector<std::vector<double>> &impulses, const std::vector<int> &imp_of, int fftsize = 1024,
+                     int hopsize = 256)
+        : V_(V), fftsize_(fftsize) {
+        std::vector<const double *> amps;
+        std::vector<size_t> lens;
+        std::vector<double> pos0;
+        for (const std::vector<double> &a : impulses) {
+            amps.push_back(a.data());
+            lens.push_back(a.size());
+            pos0.push_back((double)a.size());
+        }
+        if (imp_of.size() != V) throw std::runtime_error("maxiConvolveBank: imp_of needs one entry per stream");
+        b_ = mxg_convolve_bank_create(V, impulses.size(), amps.data(), lens.data(), pos0.data(), imp_of.data(), fftsize, hopsize);
+        if (!b_) throw std::runtime_error(std::string("mxg_convolve_bank_create: ") + mxg_last_error());
+    }
+    ~maxiConvolveBank() { if (b_) mxg_convolve_bank_destroy(b_); }
+    maxiConvolveBank(const maxiConvolveBank &) = delete;
+    maxiConvolveBank &operator=(const maxiConvolveBank &) = delete;
+    size_t size() const { return V_; }
+    int fftSize() const { return fftsize_; }
+    int frames(size_t i) const { return mxg_convolve_bank_frames(b_, i); }
+    void play(const float *d_in, size_t nblocks, float *d_out, bool as_intended = false, void *stream = nullptr) {
+        maxigpu::check(mxg_convolve_bank_play(b_, d_in, nblocks, d_out, as_intended ? 1 : 0, stream), "mxg_convolve_bank_play");
+    }
+    void play_nv(const double *d_in, size_t nblocks, double *d_out, bool as_intended = false, void *stream = nullptr) {
+        maxigpu::check(mxg_convolve_bank_play_nv(b_, d_in, nblocks, d_out, as_intended ? 1 : 0, stream), "mxg_convolve_bank_play_nv");
+    }
+    void reset() { maxigpu::check(mxg_convolve_bank_reset(b_), "mxg_convolve_bank_reset"); }
+
+private:
+    size_t V_;
+    int fftsize_;
+    mxg_convolve_bank *b_ = nullptr;
+};
+
 // ---- maxiSampler banks (L/maxiSynths.h:137-187, maxiSynths.cpp:262-491) ------------------------------------------------------
 // NS samplers of `voices` slots each over one sample; the control methods edit host copies of the slot state between renders,
 // exactly as the reference's methods edit its members; play(N) renders N calls of maxiSampler::play() for every sampler.

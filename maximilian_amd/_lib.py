@@ -183,6 +183,14 @@ SIGNATURES = {
     "mxg_convolve_reset": (c_int, [c_void_p]),
     "mxg_convolve_output": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "mxg_convolve_input": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mxg_convolve_bank_create": (c_void_p, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    "mxg_convolve_bank_destroy": (c_int, [c_void_p]),
+    "mxg_convolve_bank_reset": (c_int, [c_void_p]),
+    "mxg_convolve_bank_frames": (c_int, [c_void_p, c_size_t]),
+    "mxg_convolve_bank_impulse": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mxg_convolve_bank_play": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "mxg_convolve_bank_play_nv": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "mxg_convolve_bank_mac_host": (c_int, [c_size_t, c_int, c_int] + [c_void_p] * 11 + [c_size_t, c_void_p, c_void_p]),
     "mxg_sampler_freq_host": (c_int, [c_size_t, c_void_p, c_size_t, c_void_p]),
     "mxg_sampler_render": (c_int, [c_size_t, c_size_t, c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 12),
     "mxg_fft_features": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),

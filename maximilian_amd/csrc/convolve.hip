@@ -17,7 +17,7 @@
 
 #include <vector>
 
-#include "mxg_spectral.h"
+#include "mxg_convolve.h"
 
 struct mxg_convolve {
     int fftsize, hopsize, bins, frames;
@@ -88,50 +88,21 @@ mxg_convolve *mxg_convolve_create(const double *h_amp, size_t len, double positi
     c->fplan = nullptr; c->iplan = nullptr;
     c->d_impR = c->d_impI = c->d_tailR = c->d_tailI = c->d_sumR = c->d_sumI = c->d_obuf = nullptr;
     const int F = fftsize, bins = c->bins;
-    // the float stream setup() feeds its maxiFFT: impulse.play() x len (C:740-747), then the zero padding (:41-45)
-    const size_t total = len + (size_t)(bins - (int)(len % (size_t)bins));
-    std::vector<float> seq(total, 0.0f);
-    double position = position0;
-    for (size_t s = 0; s < len; s++) {
-        const long idx = (long)position;
-        seq[s] = (idx >= 0 && (size_t)idx < len) ? (float)h_amp[idx] : 0.0f;  // amplitudes[size] and beyond: the guard zero
-        position++;
-        if ((long)position >= (long)len) position = 0;
-    }
-    const size_t nfr = total / (size_t)F;
-    c->frames = (int)nfr;
     c->fplan = mxg_fft_plan_create(F, F, hopsize);   // maxiFFT::setup(fftsize, fftsize, hopsize): hop = window = fftsize
     c->iplan = mxg_ifft_plan_create(F, F, hopsize);  // maxiIFFT::setup(fftsize, fftsize, hopsize): Hann over `hopsize`
     bool ok = c->fplan && c->iplan;
+    ok = ok && convolve_analyse(h_amp, len, position0, c->fplan, c->h_impR, c->h_impI);  // (mxg_convolve.h)
+    const size_t nfr = ok ? c->h_impR.size() / (size_t)bins : 0;
+    c->frames = (int)nfr;
     const size_t specBytes = sizeof(float) * (nfr ? nfr : 1) * bins;
-    float *d_seq = nullptr;
-    ok = ok && hipMalloc(&d_seq, sizeof(float) * (total ? total : 1)) == hipSuccess;
     ok = ok && hipMalloc(&c->d_impR, specBytes) == hipSuccess && hipMalloc(&c->d_impI, specBytes) == hipSuccess;
     const size_t tailBytes = sizeof(float) * (nfr > 1 ? nfr - 1 : 1) * bins;
     ok = ok && hipMalloc(&c->d_tailR, tailBytes) == hipSuccess && hipMalloc(&c->d_tailI, tailBytes) == hipSuccess;
     ok = ok && hipMalloc(&c->d_sumR, sizeof(float) * bins) == hipSuccess && hipMalloc(&c->d_sumI, sizeof(float) * bins) == hipSuccess;
     ok = ok && hipMalloc(&c->d_obuf, sizeof(float) * F) == hipSuccess;
-    if (ok && nfr) {
-        ok = hipMemcpy(d_seq, seq.data(), sizeof(float) * total, hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && mxg_fft_batch(c->fplan, d_seq, (size_t)F, nfr, c->d_impR, c->d_impI, nullptr, nullptr, nullptr) == MXG_OK;
-        ok = ok && mxg_stream_sync(nullptr) == MXG_OK;
-        c->h_impR.resize(nfr * bins);
-        c->h_impI.resize(nfr * bins);
-        ok = ok && hipMemcpy(c->h_impR.data(), c->d_impR, specBytes, hipMemcpyDeviceToHost) == hipSuccess;
-        ok = ok && hipMemcpy(c->h_impI.data(), c->d_impI, specBytes, hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok) {
-            float maxReal = 0, maxImag = 0;  // :17-18, :25-32
-            for (float v : c->h_impR)
-                if (v > maxReal) maxReal = v;
-            for (float v : c->h_impI)
-                if (v > maxImag) maxImag = v;
-            for (float &v : c->h_impR) v /= maxReal;  // :47-52 (a zero maximum divides by zero there too)
-            for (float &v : c->h_impI) v /= maxImag;
-            ok = hipMemcpy(c->d_impR, c->h_impR.data(), specBytes, hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(c->d_impI, c->h_impI.data(), specBytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    }
-    if (d_seq) (void)hipFree(d_seq);
+    if (ok && nfr)
+        ok = hipMemcpy(c->d_impR, c->h_impR.data(), specBytes, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(c->d_impI, c->h_impI.data(), specBytes, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || mxg_convolve_reset(c) != MXG_OK) {
         if (ok == false && !*mxg_last_error()) fail(MXG_ERR_HIP, "mxg_convolve_create: device setup failed");
         mxg_convolve_destroy(c);

@@ -374,3 +374,66 @@ class maxiConvolve:
             self.close()
         except Exception:
             pass
+
+
+class maxiConvolveBank:
+    """A bank of V maxiConvolve objects over I shared impulses (mxg_convolve_bank_*, kernel K24).  `impulses` is a list of I
+    amplitude arrays (as maxiConvolve.setup takes one), `imp_of[v]` the impulse of stream v; one fftsize / hopsize for the bank.
+    Stream v equals, bit for bit, a maxiConvolve set up with impulses[imp_of[v]] and fed stream v's input, state carried between
+    calls.  `play(x, mode)` takes float32 [V, nblocks * fftsize]; `play_nv(x, mode)` the layout the other banks speak, float64
+    [nblocks * fftsize, V] (narrowed with a plain float cast on the way in).  `frames[i]` is impulse i's frame count."""
+
+    def __init__(self, V, impulses, imp_of, fftsize=1024, hopsize=256, positions0=None, stream=None):
+        self.h = None
+        self.stream = stream
+        amps = [np.ascontiguousarray(a, np.float64) for a in impulses]
+        I = len(amps)
+        ptrs = np.array([a.ctypes.data for a in amps], np.uintp)
+        lens = np.array([a.size for a in amps], np.uintp)
+        pos = np.array([float(a.size) for a in amps] if positions0 is None else positions0, np.float64)  # load() leaves the head at size
+        of = np.ascontiguousarray(imp_of, np.int32)
+        if of.size != V or pos.size != I:
+            raise ValueError("maxiConvolveBank: imp_of needs V entries and positions0 one per impulse")
+        h = lib().mxg_convolve_bank_create(V, I, ptrs.ctypes.data, lens.ctypes.data, pos.ctypes.data, of.ctypes.data, fftsize, hopsize)
+        if not h:
+            raise ValueError(lib().mxg_last_error().decode())
+        self.h, self.V, self.I, self.fftsize, self.hopsize, self.bins = h, V, I, fftsize, hopsize, fftsize // 2
+        self.imp_of = of
+        self.frames = [lib().mxg_convolve_bank_frames(h, i) for i in range(I)]
+
+    def impulse(self, i):
+        r = np.zeros((self.frames[i], self.bins), np.float32)
+        im = np.zeros((self.frames[i], self.bins), np.float32)
+        check(lib().mxg_convolve_bank_impulse(self.h, i, r.ctypes.data, im.ctypes.data), "mxg_convolve_bank_impulse")
+        return r, im
+
+    def _call(self, fn, name, x, dtype, mode, out):
+        if not (isinstance(x, DeviceBuffer) or hasattr(x, "data_ptr")):
+            x = DeviceBuffer.from_numpy(np.ascontiguousarray(x, dtype))
+        shape = tuple(x.shape)
+        n = int(np.prod(shape)) // self.V
+        assert n * self.V == int(np.prod(shape)) and n % self.fftsize == 0, "V streams of a whole number of fftsize blocks"
+        out = out if out is not None else DeviceBuffer(shape, dtype, zero=False)
+        check(fn(self.h, _ptr(x), n // self.fftsize, _ptr(out), mode, self.stream), name)
+        self._keep = x
+        return out
+
+    def play(self, x, mode=0, out=None):
+        return self._call(lib().mxg_convolve_bank_play, "mxg_convolve_bank_play", x, np.float32, mode, out)
+
+    def play_nv(self, x, mode=0, out=None):
+        return self._call(lib().mxg_convolve_bank_play_nv, "mxg_convolve_bank_play_nv", x, np.float64, mode, out)
+
+    def reset(self):
+        check(lib().mxg_convolve_bank_reset(self.h), "mxg_convolve_bank_reset")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mxg_convolve_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
