@@ -998,6 +998,48 @@ int mxg_sample_render(int mode, size_t V, size_t N, const double *d_samples, siz
                       int mySampleRate, const double *d_a, int aps, const double *d_start,
                       const double *d_end, double *d_position, double *d_out, void *stream);
 
+/* ---- maxiLooperBank: writable sample slots, maxiSample::loopRecord / normalise on the device (K25) ---------- */
+/* A pool of R slots of up to cap samples, zero-filled.  Slot r starts at p + r * (*stride) and is guarded with zeros on
+ * [-4, cap + 5] exactly as mxg_sample_upload guards its buffer, so p + r * stride with the slot's length is an ordinary sample
+ * pointer for mxg_sample_render*, mxg_sampler_render and the grain banks.  Returns NULL on failure; release with
+ * mxg_sample_pool_free.  mxg_sample_pool_stride(cap) is the stride such a pool has (for host arrays in the same layout). */
+double *mxg_sample_pool_alloc(size_t R, size_t cap, size_t *stride);
+int mxg_sample_pool_free(double *d_pool);
+size_t mxg_sample_pool_stride(size_t cap);
+/* The slots' lengths (amplitudes.size() per slot; slots of different lengths share a pool): refuses len[r] == 0 and
+ * len[r] > cap by name, then copies h_len [R] to d_len [R].  The render calls below take d_len; a length beyond cap that reaches
+ * them another way is read as cap, never indexed. */
+int mxg_sample_pool_lengths(size_t R, size_t cap, const uint64_t *h_len, uint64_t *d_len);
+#define MXG_LOOPER_PLAY_NONE (-1)
+/* N calls of loopRecord(in, enable, mix, start, end) (H:706-721) on every slot, each followed -- as a patch calls them -- by one
+ * call of play() (play_mode MXG_SMP_PLAY) or playLoop(pstart, pend) (MXG_SMP_PLAYLOOP) on the same slot, or by nothing
+ * (MXG_LOOPER_PLAY_NONE: d_out must be NULL).  d_in, d_out [N][R]; d_enable doubles, [R] (eps = 0) or [N][R] (eps = 1), non-zero =
+ * true as C++ converts a double to bool; d_mix, d_start, d_end, d_pstart, d_pend [R]; d_recpos (recordPosition), d_lagval (the
+ * enable lag's val, alpha 0.5) and d_position [R] in / out: trigger() zeroes recpos and position, setSample leaves position at
+ * len - 1.  Bit-exact, and independent of how the samples are split into calls (the library itself cuts a call into launches of
+ * mxg_looprec_piece() samples; a workgroup owns mxg_looprec_tile() slots).  The play head sees what this sample and earlier ones
+ * recorded.  The one departure: where the record index falls outside [0, len[r]) -- start or end outside [0, 1], start == 1,
+ * NaN, an uploaded recpos out of range; the reference indexes outside its vector -- the read gives 0, nothing is stored, and
+ * d_dropped[r] (uint32 [R], may be NULL) counts the sample.  Inside 0 <= start < 1, 0 <= end <= 1 it stays as it was.
+ * 1 <= N <= 2^24. */
+int mxg_looprec_render(size_t R, size_t N, double *d_pool, size_t stride, size_t cap, const uint64_t *d_len, const double *d_in,
+                       const double *d_enable, int eps, const double *d_mix, const double *d_start, const double *d_end, double *d_recpos,
+                       double *d_lagval, int play_mode, const double *d_pstart, const double *d_pend, double *d_position, double *d_out,
+                       uint32_t *d_dropped, void *stream);
+int mxg_looprec_piece(void);
+int mxg_looprec_tile(void);
+/* maxiSample::normalise(maxLevel[r]) (C:1126-1137) on every slot: scale = (float)(maxLevel / max|a|), a = round(scale * a); an
+ * all-zero slot becomes NaN, as in the reference.  R <= 65535. */
+int mxg_sample_pool_normalise(size_t R, double *d_pool, size_t stride, size_t cap, const uint64_t *d_len, const double *d_maxLevel,
+                              void *stream);
+/* The same functions (csrc/mxg_looper.h) on host arrays in the pool's layout (h_pool = element 0 of slot 0, with its guards around
+ * every slot); these two also refuse a bad h_len by name.  No device is touched. */
+int mxg_looprec_host(size_t R, size_t N, double *h_pool, size_t stride, size_t cap, const uint64_t *h_len, const double *h_in,
+                     const double *h_enable, int eps, const double *h_mix, const double *h_start, const double *h_end, double *h_recpos,
+                     double *h_lagval, int play_mode, const double *h_pstart, const double *h_pend, double *h_position, double *h_out,
+                     uint32_t *h_dropped);
+int mxg_sample_pool_normalise_host(size_t R, double *h_pool, size_t stride, size_t cap, const uint64_t *h_len, const double *h_maxLevel);
+
 /* maxiSample::playAtSpeedBetweenPointsFromPos(frequency, start, end, pos) (C:826-880) with the CALLER's position signal
  * d_pos [N][V]: the member `position` takes no part (it is the by-value parameter of C:823-825), so the call is a pure
  * function of its arguments.  d_freq [V] (fps = 0) or [N][V]; d_start / d_end [V] in samples.  Bit-exact. */

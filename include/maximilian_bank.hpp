@@ -1250,6 +1250,112 @@ private:
     maxigpu::DeviceArray<double> d_alpha_, d_recip_, d_val_;
 };
 
+// R writable maxiSample slots on the device (mxg_sample_pool_alloc, K25): loopRecord (H:706-721) over blocks [N][R] that other
+// banks rendered, one play head per slot -- play() or playLoop() -- fused behind the record head in the reference's call order,
+// and normalise (C:1126-1137).  Bit-exact and independent of how the samples are split into calls; a record index outside
+// [0, len) reads 0, stores nothing and is counted (dropped()).  deviceSamples(r) / getLength(r) feed mxg_sample_render*.
+class maxiLooperBank {
+public:
+    maxiLooperBank(size_t slots, size_t capacity) : R(slots), cap_(capacity), len_(slots, capacity) {
+        maxigpu::check(mxg_init(-1), "mxg_init");
+        pool_ = mxg_sample_pool_alloc(R, cap_, &stride_);
+        if (!pool_) throw std::runtime_error(std::string("mxg_sample_pool_alloc: ") + mxg_last_error());
+        d_len_.resize(R);
+        pushLengths();
+        d_recpos_.resize(R);
+        d_lag_.resize(R);
+        d_dropped_.resize(R);
+        d_position_.upload(std::vector<double>(R, (double)capacity - 1.0));
+        d_mix_.upload(std::vector<double>(R, 0.5));
+        d_start_.upload(std::vector<double>(R, 0.0));
+        d_end_.upload(std::vector<double>(R, 1.0));
+        d_pstart_.upload(std::vector<double>(R, 0.0));
+        d_pend_.upload(std::vector<double>(R, 1.0));
+    }
+    maxiLooperBank(const maxiLooperBank &) = delete;
+    maxiLooperBank &operator=(const maxiLooperBank &) = delete;
+    ~maxiLooperBank() { mxg_sample_pool_free(pool_); }
+    size_t slots() const { return R; }
+    size_t capacity() const { return cap_; }
+    size_t stride() const { return stride_; }
+    double *deviceSamples(size_t r) const { return pool_ + r * stride_; }
+    size_t getLength(size_t r) const { return (size_t)len_[r]; }
+    // maxiSample::setSample (H:670-678) on one slot: the data, zeros up to the capacity, position = len - 1
+    void setSample(size_t r, const std::vector<double> &data) {
+        if (data.empty() || data.size() > cap_) throw std::invalid_argument("maxiLooperBank::setSample: the data does not fit the slot");
+        std::vector<double> full(cap_, 0.0);
+        std::copy(data.begin(), data.end(), full.begin());
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        maxigpu::check(mxg_memcpy_h2d(deviceSamples(r), full.data(), cap_ * sizeof(double), nullptr), "mxg_memcpy_h2d");
+        len_[r] = data.size();
+        pushLengths();
+        const double pos = (double)data.size() - 1.0;
+        d_position_.upload(&pos, 1, r);
+    }
+    void setLength(size_t r, size_t n) {
+        const uint64_t old = len_[r];
+        len_[r] = n;
+        try {
+            pushLengths();
+        } catch (...) {
+            len_[r] = old;
+            throw;
+        }
+    }
+    void trigger() {  // C:597-600 on every slot
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_position_.upload(std::vector<double>(R, 0.0));
+        d_recpos_.upload(std::vector<double>(R, 0.0));
+    }
+    void setRecordMix(double mix) { spread(d_mix_, mix); }
+    void setLoop(double start, double end) { spread(d_start_, start); spread(d_end_, end); }
+    void setPlayLoop(double start, double end) { spread(d_pstart_, start); spread(d_pend_, end); }
+    // d_enable: [N][R] doubles (perSample) or [R]; non-zero = true
+    void loopRecord(size_t N, const double *d_in, const double *d_enable, bool perSample, void *stream = nullptr) {
+        render(N, d_in, d_enable, perSample, MXG_LOOPER_PLAY_NONE, nullptr, stream);
+    }
+    void play(size_t N, const double *d_in, const double *d_enable, bool perSample, double *d_out, void *stream = nullptr) {
+        render(N, d_in, d_enable, perSample, MXG_SMP_PLAY, d_out, stream);
+    }
+    void playLoop(size_t N, const double *d_in, const double *d_enable, bool perSample, double *d_out, void *stream = nullptr) {
+        render(N, d_in, d_enable, perSample, MXG_SMP_PLAYLOOP, d_out, stream);
+    }
+    void normalise(double maxLevel = 0.99, void *stream = nullptr) {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_level_.upload(std::vector<double>(R, maxLevel));
+        maxigpu::check(mxg_sample_pool_normalise(R, pool_, stride_, cap_, d_len_.get(), d_level_.get(), stream), "mxg_sample_pool_normalise");
+    }
+    std::vector<double> download(size_t r) const {
+        std::vector<double> h(getLength(r));
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        maxigpu::check(mxg_memcpy_d2h(h.data(), deviceSamples(r), h.size() * sizeof(double), nullptr), "mxg_memcpy_d2h");
+        return h;
+    }
+    std::vector<uint32_t> dropped() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_dropped_.download(); }
+    std::vector<double> recordPosition() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_recpos_.download(); }
+    std::vector<double> position() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_position_.download(); }
+    std::vector<double> lagValue() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_lag_.download(); }
+
+private:
+    void pushLengths() { maxigpu::check(mxg_sample_pool_lengths(R, cap_, len_.data(), d_len_.get()), "mxg_sample_pool_lengths"); }
+    void spread(maxigpu::DeviceArray<double> &a, double x) {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        a.upload(std::vector<double>(R, x));
+    }
+    void render(size_t N, const double *d_in, const double *d_enable, bool perSample, int mode, double *d_out, void *stream) {
+        maxigpu::check(mxg_looprec_render(R, N, pool_, stride_, cap_, d_len_.get(), d_in, d_enable, perSample ? 1 : 0, d_mix_.get(),
+                                          d_start_.get(), d_end_.get(), d_recpos_.get(), d_lag_.get(), mode, d_pstart_.get(), d_pend_.get(),
+                                          d_position_.get(), d_out, d_dropped_.get(), stream),
+                       "mxg_looprec_render");
+    }
+    size_t R, cap_, stride_ = 0;
+    double *pool_ = nullptr;
+    std::vector<uint64_t> len_;
+    maxigpu::DeviceArray<uint64_t> d_len_;
+    maxigpu::DeviceArray<uint32_t> d_dropped_;
+    maxigpu::DeviceArray<double> d_recpos_, d_lag_, d_position_, d_mix_, d_start_, d_end_, d_pstart_, d_pend_, d_level_;
+};
+
 // V x maxiMap / maxiConvert (mxg_map_render): stateless, flat over the block; d_out may be d_in.  Ranges are one value for the
 // bank or one per voice.  linlin and clamp are the reference's bits; the other four use the device's pow / log / log10.
 class maxiMapBank {

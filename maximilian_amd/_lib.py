@@ -166,6 +166,18 @@ SIGNATURES = {
     "mxg_sample_free": (c_int, [c_void_p]),
     "mxg_sample_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_sample_pool_alloc": (c_void_p, [c_size_t, c_size_t, POINTER(c_size_t)]),
+    "mxg_sample_pool_free": (c_int, [c_void_p]),
+    "mxg_sample_pool_stride": (c_size_t, [c_size_t]),
+    "mxg_sample_pool_lengths": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p]),
+    "mxg_looprec_render": (c_int, [c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_int] +
+                           [c_void_p] * 6),
+    "mxg_looprec_host": (c_int, [c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_int] +
+                         [c_void_p] * 5),
+    "mxg_looprec_piece": (c_int, []),
+    "mxg_looprec_tile": (c_int, []),
+    "mxg_sample_pool_normalise": (c_int, [c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mxg_sample_pool_normalise_host": (c_int, [c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "mxg_fft_plan_create": (c_void_p, [c_int, c_int, c_int]),
     "mxg_fft_plan_destroy": (c_int, [c_void_p]),
     "mxg_fft_plan_bins": (c_int, [c_void_p]),

@@ -2354,3 +2354,134 @@ class maxiAtomBank:
             self.free()
         except Exception:
             pass
+
+
+LOOPER_PLAY = {"none": -1, "play": 0, "playLoop": 2}
+
+
+class maxiLooperBank(_Bank):
+    """R writable maxiSample slots on the device (mxg_sample_pool_alloc, K25): loopRecord (H:706-721) over blocks that other banks
+    rendered, with one play head per slot -- play() or playLoop() -- fused behind the record head in the reference's call order,
+    and normalise (C:1126-1137).  Bit-exact, and independent of how the samples are split into calls.  The one departure: a record
+    index outside [0, len) reads 0, stores nothing and is counted in `dropped`.  slot_pointer(r) with length(r) is an ordinary
+    sample pointer for maxiSampleBank, the sampler and the grain banks."""
+
+    def __init__(self, slots, capacity, stream=None):
+        super().__init__(slots, stream)
+        self.R, self.cap = int(slots), int(capacity)
+        st = ctypes.c_size_t(0)
+        self.pool = lib().mxg_sample_pool_alloc(self.R, self.cap, ctypes.byref(st))
+        if not self.pool:
+            raise MemoryError(lib().mxg_last_error().decode())
+        self.stride = st.value
+        self.lengths = np.full(self.R, self.cap, np.uint64)
+        self.len = DeviceBuffer(self.R, np.uint64)
+        self._set_lengths()
+        self.recpos, self.lagval = DeviceBuffer(self.R), DeviceBuffer(self.R)
+        self.position = DeviceBuffer.from_numpy(self.lengths.astype(np.float64) - 1.0)
+        self.mix, self.start, self.end = DeviceBuffer.from_numpy(np.full(self.R, 0.5)), DeviceBuffer(self.R), DeviceBuffer.from_numpy(np.ones(self.R))
+        self.pstart, self.pend = DeviceBuffer(self.R), DeviceBuffer.from_numpy(np.ones(self.R))
+        self.dropped = DeviceBuffer(self.R, np.uint32)
+
+    def _set_lengths(self):
+        check(lib().mxg_sample_pool_lengths(self.R, self.cap, self.lengths.ctypes.data, self.len.ptr), "mxg_sample_pool_lengths")
+
+    def _vec(self, buf, x):
+        buf.upload(np.broadcast_to(np.asarray(x, np.float64), (self.R,)))
+
+    def length(self, r):
+        return int(self.lengths[r])
+
+    def slot_pointer(self, r):
+        """Device address of element 0 of slot r."""
+        return self.pool + 8 * self.stride * int(r)
+
+    def setSample(self, slot, data):
+        """maxiSample::setSample (H:670-678) on one slot: the data, zeros up to the capacity, position = len - 1."""
+        a = np.ascontiguousarray(data, np.float64)
+        if not 0 < a.size <= self.cap:
+            raise ValueError("maxiLooperBank.setSample: %d samples do not fit a slot of %d" % (a.size, self.cap))
+        full = np.zeros(self.cap)
+        full[:a.size] = a
+        check(lib().mxg_sync(), "mxg_sync")
+        check(lib().mxg_memcpy_h2d(self.slot_pointer(slot), full.ctypes.data, full.nbytes, None), "mxg_memcpy_h2d")
+        self.lengths[slot] = a.size
+        self._set_lengths()
+        pos = self.position.numpy()
+        pos[slot] = a.size - 1.0
+        self.position.upload(pos)
+
+    def setLength(self, slot, n):
+        """An empty (or kept) slot of n samples, as setSample of that many zeros would leave its length."""
+        old = self.lengths.copy()
+        self.lengths[slot] = int(n)
+        try:
+            self._set_lengths()
+        except Exception:
+            self.lengths = old
+            raise
+
+    def trigger(self):
+        """maxiSample::trigger (C:597-600) on every slot: position = recordPosition = 0."""
+        self._vec(self.position, 0.0)
+        self._vec(self.recpos, 0.0)
+
+    def setRecordMix(self, x):
+        self._vec(self.mix, x)
+
+    def setLoop(self, start, end):
+        self._vec(self.start, start)
+        self._vec(self.end, end)
+
+    def setPlayLoop(self, start, end):
+        self._vec(self.pstart, start)
+        self._vec(self.pend, end)
+
+    def loopRecord(self, x, enable, N=None, play="none", out=None):
+        """N calls of loopRecord on every slot.  x: device block [N][R]; enable: a device block [N][R] (a gate block of another
+        bank: non-zero = true), or a scalar / array [R] for the whole call.  play = "play" | "playLoop": the fused head's block
+        [N][R] is returned."""
+        N = int(x.shape[0] if N is None else N)
+        _fx_input(x, self.R, N)
+        mode = LOOPER_PLAY[play] if isinstance(play, str) else int(play)
+        if isinstance(enable, DeviceBuffer) or hasattr(enable, "data_ptr"):
+            eps = int(tuple(enable.shape) != (self.R,))
+            if eps:
+                _fx_dev(enable, np.float64, "enable", (N * self.R,))
+        else:
+            enable, eps = DeviceBuffer.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(enable, np.float64), (self.R,)))), 0
+        if mode != -1:
+            out = self._out(N, out)
+        check(lib().mxg_looprec_render(self.R, N, self.pool, self.stride, self.cap, self.len.ptr, _ptr(x), _ptr(enable), eps, self.mix.ptr,
+                                       self.start.ptr, self.end.ptr, self.recpos.ptr, self.lagval.ptr, mode, self.pstart.ptr, self.pend.ptr,
+                                       self.position.ptr, _ptr(out) if mode != -1 else None, self.dropped.ptr, self.stream), "mxg_looprec_render")
+        self._keep = (x, enable)   # (alive until the stream has run the launches)
+        return out if mode != -1 else None
+
+    def play(self, x, enable, N=None, out=None):
+        return self.loopRecord(x, enable, N, "play", out)
+
+    def playLoop(self, x, enable, N=None, out=None):
+        return self.loopRecord(x, enable, N, "playLoop", out)
+
+    def normalise(self, maxLevel=0.99):
+        lv = DeviceBuffer.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(maxLevel, np.float64), (self.R,))))
+        check(lib().mxg_sample_pool_normalise(self.R, self.pool, self.stride, self.cap, self.len.ptr, lv.ptr, self.stream), "mxg_sample_pool_normalise")
+        self.sync()
+
+    def download(self, slot):
+        out = np.empty(self.length(slot))
+        check(lib().mxg_sync(), "mxg_sync")
+        check(lib().mxg_memcpy_d2h(out.ctypes.data, self.slot_pointer(slot), out.nbytes, None), "mxg_memcpy_d2h")
+        return out
+
+    def free(self):
+        if getattr(self, "pool", None):
+            lib().mxg_sample_pool_free(self.pool)
+            self.pool = None
+
+    def __del__(self):  # best effort
+        try:
+            self.free()
+        except Exception:
+            pass
