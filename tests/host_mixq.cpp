@@ -11,7 +11,9 @@
 // results -- read through result() after flush, through release()-ordered asynchronous reads, and through the host sink
 // ring -- must equal the sum over ranks for every block of every batch.
 // Built a second time with -DMXG_MIXQ_MUTATE_NO_SLOT_WAIT (the wait that protects a staging buffer from being refilled
-// while its reduce still reads it is compiled out): the harness must then REPORT corruption, which shows the check has teeth.
+// while its reduce still reads it is compiled out) and a third with -DMXG_MIXQ_MUTATE_NO_CONSUMED_WAIT (the wait that keeps a reduce
+// from overwriting a result under a declared asynchronous read): the harness must then REPORT corruption, which shows the check
+// has teeth.  The first is a race the harness has to win; the second is caught in every run by the gated reads of run_case.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -33,6 +35,7 @@ struct FakeEvent {
     std::mutex mu;
     std::condition_variable cv;
     unsigned long recorded = 0, done = 0;
+    int blocked = 0;  // stream operations waiting for this event right now (what a gated read looks at, see run_case)
 };
 
 struct FakeStream {
@@ -126,7 +129,10 @@ struct FakeDev {
         }
         s->enqueue([e, g] {
             std::unique_lock<std::mutex> lk(e->mu);
+            if (e->done >= g) return;
+            e->blocked++;
             e->cv.wait(lk, [e, g] { return e->done >= g; });
+            e->blocked--;
         });
         return 0;
     }
@@ -194,7 +200,13 @@ struct RankCtx {
 
 // groups > 1: a slot is [groups][block] rows -- row 0 carries value(), row g > 0 the constant g (all exact), so the fold's sum is
 // value + groups (groups - 1) / 2
-int run_case(size_t block, int depth, size_t blocks, int delay_us, unsigned seed, bool verbose, size_t groups = 1) {
+// gate: the asynchronous read of batch n (n + 2 < batches) is HELD until the protocol has shown what it does about the reduce of batch
+// n + 2, which writes the same result buffer: either that reduce has finished on the fabric (then the read returns batch n + 2's sums
+// and the case fails), or rank 0's queue stream is blocked on consumed[b], the event release() records behind this very read.  One of
+// the two always happens, whatever the threads' timing: the hosts never wait for the reader, so batch n + 2 is always submitted.  A
+// queue that does not order the reduce behind the declared read is thereby caught in every run, not only when the reader loses a race.
+int run_case(size_t block, int depth, size_t blocks, int delay_us, unsigned seed, bool verbose, size_t groups = 1, bool gate = false) {
+    const size_t expect_batches = (blocks + (size_t)depth - 1) / (size_t)depth;
     Fabric fab;
     std::atomic<int> errors{0};
     RankCtx R[2];
@@ -258,7 +270,21 @@ int run_case(size_t block, int depth, size_t blocks, int delay_us, unsigned seed
                 const double *res = c.q.result[b];
                 c.dev.wait(c.reader.get(), c.q.reduced[b]);
                 double *dst = seen.data() + batch_first * block;
-                c.reader->enqueue([res, dst, nb, block] {
+                const size_t n = c.q.batches - 1;  // this batch: collective n on the fabric, which counts n + 1 finished behind it
+                FakeEvent *cons = gate && n + 2 < expect_batches ? c.q.consumed[b] : nullptr;
+                Fabric *f = &fab;
+                c.reader->enqueue([res, dst, nb, block, cons, f, n] {
+                    for (bool held = cons != nullptr; held;) {
+                        {
+                            std::lock_guard<std::mutex> lk(f->mu);
+                            if (f->finished >= n + 3) held = false;
+                        }
+                        {
+                            std::lock_guard<std::mutex> lk(cons->mu);
+                            if (cons->blocked > 0) held = false;
+                        }
+                        if (held) std::this_thread::sleep_for(std::chrono::microseconds(20));
+                    }
                     for (size_t i = 0; i < nb * block; i++) {
                         dst[i] = res[i];
                         if ((i & 31) == 0) std::this_thread::yield();
@@ -317,12 +343,11 @@ int run_case(size_t block, int depth, size_t blocks, int delay_us, unsigned seed
             for (size_t i = 0; i < block; i++)
                 if (c.sink[(k % ring) * block + i] != value(0, k, i) + value(1, k, i) + gsum) bad_sink++;
     }
-    const size_t expect_batches = (blocks + (size_t)depth - 1) / (size_t)depth;
     int bad = errors.load() + (R[0].q.batches != expect_batches) + (R[1].q.batches != expect_batches);
     if (verbose || bad || bad_seen || bad_sink || bad_last)
-        printf("case block=%zu depth=%d blocks=%zu groups=%zu delay=%dus seed=%u: batches %zu/%zu, wrong async reads %zu, wrong sink %zu, "
+        printf("case block=%zu depth=%d blocks=%zu groups=%zu delay=%dus seed=%u%s: batches %zu/%zu, wrong async reads %zu, wrong sink %zu, "
                "wrong last result %zu, protocol errors %d\n",
-               block, depth, blocks, groups, delay_us, seed, R[0].q.batches, expect_batches, bad_seen, bad_sink, bad_last, errors.load());
+               block, depth, blocks, groups, delay_us, seed, gate ? " gated reads" : "", R[0].q.batches, expect_batches, bad_seen, bad_sink, bad_last, errors.load());
     return bad + (bad_seen != 0) + (bad_sink != 0) + (bad_last != 0);
 }
 
@@ -333,18 +358,19 @@ int main(int argc, char **argv) {
     int failed = 0, cases = 0;
     for (int rnd = 0; rnd < rounds; rnd++) {
         // (block doubles, depth M, blocks): full batches only, a partial last batch, depth 1 (config 5's one reduce per
-        // render), long runs with many batches in flight
+        // render), long runs with many batches in flight.  Every other case holds its asynchronous reads (run_case, `gate`); a round has
+        // nine cases, so every configuration runs both ways in two rounds
         const size_t cfg[][3] = {{64, 3, 7}, {1024, 16, 80}, {256, 1, 9}, {32, 4, 64}, {128, 5, 23}, {16, 2, 41}};
         for (auto &c : cfg) {
             failed += run_case(c[0], (int)c[1], c[2], rnd % 3 == 0 ? 0 : 40 * (rnd % 3), 1000u + (unsigned)rnd * 97u + (unsigned)cases,
-                               false) != 0;
+                               false, 1, cases % 2 == 1) != 0;
             cases++;
         }
         // grouped slots (the config-2 step: the queue folds [groups][block] rows per block on its own stream before the reduce)
         const size_t gcfg[][4] = {{64, 3, 7, 4}, {128, 16, 50, 3}, {32, 2, 21, 7}};
         for (auto &c : gcfg) {
             failed += run_case(c[0], (int)c[1], c[2], rnd % 3 == 0 ? 0 : 40 * (rnd % 3), 5000u + (unsigned)rnd * 89u + (unsigned)cases,
-                               false, c[3]) != 0;
+                               false, c[3], cases % 2 == 1) != 0;
             cases++;
         }
     }

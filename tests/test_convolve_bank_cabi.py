@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import convolve_host as ch
 from conftest import ROOT
 
 NEW = ["mxg_convolve_bank_create", "mxg_convolve_bank_destroy", "mxg_convolve_bank_reset", "mxg_convolve_bank_frames",
@@ -36,6 +37,7 @@ def test_symbols_declared_exported_and_bound():
     hpp = open(os.path.join(ROOT, "include", "maximilian_bank.hpp")).read()
     assert re.search(r"\bclass maxiConvolveBank\b", hpp) and "mxg_convolve_bank_play_nv" in hpp
     assert re.search(r"kConvM = %d\b" % TILE, open(os.path.join(ROOT, "maximilian_amd", "csrc", "mxg_convolve.h")).read())
+    assert re.search(r"kChunk = %d\b" % ch.KCHUNK, open(os.path.join(ROOT, "maximilian_amd", "csrc", "convolve_bank.hip")).read())
 
 
 class Naive:
@@ -76,9 +78,59 @@ def test_mac_host_against_numpy(bins, R, Ks, calls):
     """V = 3 streams on I = 2 impulses (imp_of = [0, 1, 0]) of K in {0, 1, 5} frames; a ring of capacity 5 = max K (one frame per launch:
     every call wraps it, and the calls of 5 and 7 exceed it) and one of 9 (launches of up to 5 frames: a full tile and a ragged one, the
     call of 7 in two launches); no call is a multiple of the tile of 4.  Bin 0 carries imaginary parts; one input value is +Inf."""
+    assert all(n % TILE for n in calls)
+    mac_host_against_numpy(bins, R, Ks, calls)
+
+
+DEVICE_CALLS = ([45], [19, 1, 2, 23], [3, 16, 1, 20, 5])
+
+
+@pytest.mark.parametrize("bins", [4, 32, 512, 4096])
+@pytest.mark.parametrize("Ks", [(5, 1), (0, 5)])
+@pytest.mark.parametrize("calls", DEVICE_CALLS)
+def test_mac_host_against_numpy_device_ring(bins, Ks, calls):
+    """The same at the ring the DEVICE gives these impulses, R = max K + 15 = 20 rows in chunks of 16 frames, and the calls of
+    tests/test_gpu_convolve_bank.py's wrap cases: 45 frames wrap the ring twice, the calls together straddle its end, land on slot 0,
+    read history across the end and span chunks (tests/convolve_host.py).  bins 4 is two lanes a row, the fewest the entry point takes;
+    4096 is fftsize 8192.  The lane text is thereby pinned to numpy at the geometry the GPU tests run: what remains device-only is
+    the head word, the advance kernel, the chunk loop's launch arguments and the block decode of convolve_bank.hip."""
+    R = ch.ring_rows(Ks)
+    assert R == max(Ks) + 15 == 20
+    assert set().union(*(ch.ring_events(R, max(Ks), c) for c in DEVICE_CALLS)) == ch.EVENTS
+    assert ch.ring_events(R, max(Ks), DEVICE_CALLS[1]) == ch.EVENTS
+    mac_host_against_numpy(bins, R, Ks, calls)
+
+
+def test_ring_model_and_the_gpu_cases_inputs():
+    """tests/convolve_host.py's model of the head at splits worked through by hand, and the condition the GPU tests put on their own
+    inputs, checked here as well so that it is seen without a GPU: every case feeds more blocks than R + max K, the splits of a wrap case
+    produce all four events together, the split of a geometry case alone."""
+    ev = ch.ring_events
+    assert ev(20, 5, [11]) == set() and ev(20, 5, [2, 7, 1, 1]) == set()           # what the suite ran before: no event at all
+    assert ev(20, 5, [17]) == {"later_chunk"}
+    assert ev(20, 5, [16, 4]) == {"lands_on_0"} and ev(20, 5, [16, 5]) == {"store_wrap"}
+    assert ev(20, 5, [16, 4, 1]) == {"lands_on_0", "read_wrap"}                     # head 0 on a ring that holds frames
+    assert ev(20, 5, [3, 1]) == set()                                               # head 3 < K - 1 on a fresh ring: the rows read are reset()'s
+    assert ev(20, 5, [16, 7, 1]) == {"store_wrap", "read_wrap"} and ev(20, 5, [16, 8, 1]) == {"store_wrap"}   # heads 3 and 4 = K - 1
+    assert ev(20, 1, [16, 4, 1]) == {"lands_on_0"}                                  # K = 1 reads no history
+    assert ev(20, 5, [45]) == {"later_chunk", "store_wrap"} and ev(20, 5, [19, 1, 2, 23]) == ch.EVENTS
+    assert ev(54, 39, [54, 33, 25]) == ch.EVENTS and ev(54, 39, [38, 16, 58]) == ch.EVENTS and ev(17, 2, [1, 16, 20]) == ch.EVENTS
+    assert ch.ring_head(20, [45]) == 5 and ch.ring_head(20, [19, 1, 2, 23]) == 5 and ch.ring_head(17, [17, 17, 3]) == 3
+    assert ch.frames_of(300, 64) == 5 and ch.frames_of(20, 64) == 0 and ch.frames_of(40000, 1024) == 39 and ch.frames_of(30, 8) == 4
+    assert sorted(c[0] for c in ch.GEOMETRY_CASES.values()) == [8, 16, 256, 512, 1024, 2048, 4096, 8192]
+    for name, (F, H, lens, splits) in ch.ALL_CASES.items():
+        frames = ch.case_frames(name)
+        R, Kmax = ch.ring_rows(frames), max(frames)
+        assert Kmax >= 2 and min(frames) <= 1 and 0 < H <= F, name
+        assert ch.case_blocks(name) > R + Kmax, name
+        each = [ev(R, Kmax, s) for s in splits]
+        assert set().union(*each) == ch.EVENTS, name
+        assert name in ch.WRAP_CASES or each == [ch.EVENTS], name
+
+
+def mac_host_against_numpy(bins, R, Ks, calls):
     import maximilian_amd as m
     lib = m.lib()
-    assert all(n % TILE for n in calls)
     V, imp_of = 3, [0, 1, 0]
     rng = np.random.default_rng(bins + 7 * R + 31 * Ks[0] + len(calls))
     rows = sum(Ks)

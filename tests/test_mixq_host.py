@@ -32,6 +32,8 @@ def test_mix_queue_harness_catches_a_missing_wait(tmp_path, mutant):
     exe = _build(tmp_path, "mixq_mut", ["-D" + mutant])
     # the mutants are RACES: whether one shows in a given run depends on the worker threads' timing (a loaded machine can hide
     # it for 108 cases).  The harness has to catch it within a few attempts of growing length, not necessarily in the first.
+    # (The missing consumed wait no longer depends on timing: every other case of host_mixq.cpp holds its asynchronous reads until
+    # the queue has either ordered the next reduce into that buffer behind them or let it through.)
     out = ""
     for rounds in ("12", "24", "48", "96"):
         r = subprocess.run([exe, rounds], capture_output=True, text=True, timeout=600)

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import convolve_host as ch
 from conftest import assert_bits_equal
 
 CASES = [(1024, 1024, 1024), (1024, 256, 0), (512, 128, 512), (2048, 1024, 2048), (64, 64, 64)]
@@ -129,11 +130,25 @@ def test_convolve_port_matches_golden(port, golden, tag):
     assert not g["out0_" + tag].any() and np.abs(g["out1_" + tag]).max() > 0.01
 
 
+# (fftsize, hopsize, impulse length, blocks): every launch geometry of maxiConvolveBank, at more blocks than its ring has rows
+CONVOLVE_RING_SHAPES = [(8, 8, 30, 45), (8, 4, 30, 45), (16, 4, 50, 45), (64, 16, 300, 45), (64, 64, 300, 45), (256, 64, 700, 40),
+                        (512, 128, 1300, 40), (1024, 256, 2600, 40), (1024, 512, 40000, 112), (2048, 512, 5000, 38),
+                        (4096, 1024, 9000, 38), (8192, 2048, 20000, 37), (8192, 8192, 9000, 37)]
+
+
 def test_convolve_port_matches_reference(port, ref):
+    """The port is the reference side of every GPU test of maxiConvolve and maxiConvolveBank: it is pinned to the compiled reference
+    at a few short shapes, at CONVOLVE_RING_SHAPES, and at every shape tests/test_gpu_convolve_bank.py runs beyond one ring
+    (convolve_host.ALL_CASES: both impulse lengths at the case's block count), outputs and both impulse planes, both modes."""
     rng = np.random.default_rng(99)
-    for Li, F, H in [(700, 64, 16), (6000, 512, 128), (2049, 1024, 256), (100, 1024, 256)]:
+    shapes = [(Li, F, H, F * 5 + 7) for Li, F, H in [(700, 64, 16), (6000, 512, 128), (2049, 1024, 256), (100, 1024, 256)]]
+    shapes += [(Li, F, H, F * nb) for F, H, Li, nb in CONVOLVE_RING_SHAPES]
+    shapes += [(Li, F, H, F * ch.case_blocks(name)) for name, (F, H, lens, _) in ch.ALL_CASES.items() for Li in lens]
+    shapes = list(dict.fromkeys(shapes))
+    assert len(shapes) >= 4 + len(CONVOLVE_RING_SHAPES)
+    for Li, F, H, n in shapes:
         pcm = (rng.uniform(-1, 1, Li) * 20000).astype(np.int16)
-        x = rng.uniform(-1, 1, F * 5 + 7).astype(np.float32)
+        x = rng.uniform(-1, 1, n).astype(np.float32)
         for mode in (0, 1):
             a, b = ref.convolve(pcm, x, F, H, mode), port.convolve(pcm, x, F, H, mode)
             for which, (u, v) in enumerate(zip(a, b)):
