@@ -683,6 +683,18 @@ int mxg_kuramoto_render(int mode, size_t S, size_t N, size_t B, const double *d_
                         int K_per_sample, double *d_phase, double *d_gathered, int32_t *d_update, int want, double *d_mix,
                         double *d_phases_out, void *stream);
 
+/* ---- the same classes for sets of up to 1024 oscillators (K26) ------------------------------------------------------------
+ * mxg_kuramoto_wide_render: the arguments, layouts, mode and want bits of mxg_kuramoto_render, for N = 1 .. 1024 (0 and more than
+ * 1024 are refused without a launch).  One workgroup per set and one lane per oscillator, two workgroup barriers per sample: it
+ * pays from N = 65 on; for N <= 64 it is accepted and gives mxg_kuramoto_render's bits, but with one set per workgroup instead of
+ * 64 / W per wavefront.  The results are bit-identical to the host build of maximilian_amd/csrc/mxg_kuramoto.h
+ * (tests/host_kuramoto_wide.cpp) and stay within the reference's own accumulated rounding.  The choice
+ * between the trusted and the general sine, and the async skip, look at all phases of the SET (not of the wavefront). */
+#define MXG_KURA_WIDE_MAX_N 1024
+int mxg_kuramoto_wide_render(int mode, size_t S, size_t N, size_t B, const double *d_freq, int freq_per_sample, const double *d_K,
+                             int K_per_sample, double *d_phase, double *d_gathered, int32_t *d_update, int want, double *d_mix,
+                             double *d_phases_out, void *stream);
+
 /* ---- shapers, cross-fade, select and line: maxiNonlinearity / maxiDistortion, maxiXFade, maxiSelect(X), maxiLine (K18) ----
  * (H:1046-1139, 1491-1617, 2018-2088.)  All blocks are [N][V] doubles.  The first three are streams without a recurrence over
  * time: flat over the N * V elements, 16-byte accesses where every pointer is 16-byte aligned (else, and with the knob rw_store

@@ -898,6 +898,73 @@ private:
     maxigpu::DeviceArray<int32_t> update_;
 };
 
+// maxiKuramotoBank for sets of N = 1 .. 1024 oscillators (mxg_kuramoto_wide_render, kernel K26: one workgroup per set, one lane
+// per oscillator).  The same surface; it pays from N = 65 on -- up to 64 both give the same bits and maxiKuramotoBank packs
+// several sets into a wavefront.  The exact form is N * N sines per set and sample; meanfield is N sine / cosine pairs.
+class maxiKuramotoWideBank {
+public:
+    maxiKuramotoWideBank(size_t sets, size_t N, bool meanfield = false, bool asynchronous = false)
+        : S(sets), N_(N), mode((meanfield ? MXG_KURA_MEANFIELD : 0) | (asynchronous ? MXG_KURA_ASYNC : 0)) {
+        if (N_ < 1 || N_ > MXG_KURA_WIDE_MAX_N) throw std::runtime_error("maxiKuramotoWideBank: a set has 1 .. 1024 oscillators");
+        freq_.resize(S);
+        K_.resize(S);
+        reset();
+    }
+    void reset() {  // fresh sets: phases 0, gathered phases 0, flags down
+        phase_.resize(S * N_);
+        if (mode & MXG_KURA_ASYNC) { gathered_.resize(S * N_); update_.resize(S); }
+    }
+    size_t sets() const { return S; }
+    size_t size() const { return N_; }
+    void setFreq(const std::vector<double> &f) { per_set(f, freq_, "setFreq"); }
+    void setFreq(double f) { setFreq(std::vector<double>(S, f)); }
+    void setK(const std::vector<double> &k) { per_set(k, K_, "setK"); }
+    void setK(double k) { setK(std::vector<double>(S, k)); }
+    // [S][N], set-major
+    void setPhases(const std::vector<double> &phases) {
+        if (phases.size() != S * N_) throw std::runtime_error("maxiKuramotoWideBank::setPhases: S * N phases");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        phase_.upload(phases);
+        if (mode & MXG_KURA_ASYNC) update_.upload(std::vector<int32_t>(S, 1));
+    }
+    void setPhase(double phase, size_t oscillatorIdx, size_t set) {
+        if (set >= S || oscillatorIdx >= N_) throw std::runtime_error("maxiKuramotoWideBank::setPhase: no such oscillator");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        phase_.upload(&phase, 1, set * N_ + oscillatorIdx);
+        const int32_t one = 1;
+        if (mode & MXG_KURA_ASYNC) update_.upload(&one, 1, set);
+    }
+    std::vector<double> phases() const {  // getPhase(i) of every set, [S][N]
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        return phase_.download();
+    }
+    // d_mix [B][S] and / or d_phases_out [B][S][N] (null: not rendered); d_freq / d_K: null = the bank's per-set values, else a
+    // block [B][S]
+    void play(size_t B, double *d_mix, double *d_phases_out = nullptr, const double *d_freq = nullptr, const double *d_K = nullptr,
+              void *stream = nullptr) {
+        const int want = (d_mix ? MXG_KURA_WANT_MIX : 0) | (d_phases_out ? MXG_KURA_WANT_PHASES : 0);
+        maxigpu::check(mxg_kuramoto_wide_render(mode, S, N_, B, d_freq ? d_freq : freq_.get(), d_freq ? 1 : 0, d_K ? d_K : K_.get(),
+                                                d_K ? 1 : 0, phase_.get(), gathered_.get(), update_.get(), want, d_mix, d_phases_out,
+                                                stream),
+                       "mxg_kuramoto_wide_render");
+    }
+    // state arrays on the device (include/maxigpu.h)
+    double *phase() { return phase_.get(); }
+    double *gathered() { return gathered_.get(); }
+    int32_t *update() { return update_.get(); }
+
+private:
+    void per_set(const std::vector<double> &v, maxigpu::DeviceArray<double> &d, const char *what) {
+        if (v.size() != S) throw std::runtime_error(std::string("maxiKuramotoWideBank::") + what + ": one value per set");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d.upload(v);
+    }
+    size_t S, N_;
+    int mode;
+    maxigpu::DeviceArray<double> freq_, K_, phase_, gathered_;
+    maxigpu::DeviceArray<int32_t> update_;
+};
+
 // ---- shapers, cross-fade, select and line (H:1046-1139, 1491-1617, 2018-2088; kernel K18) ----------------------------
 // The small classes that sit BETWEEN the other banks: every block is [N][V] on the device, so a chain such as oscillator ->
 // distortion -> filter, or "cross-fade two banks by a line", never leaves it.  The first three are stateless.

@@ -124,6 +124,8 @@ SIGNATURES = {
                             [c_int] + [c_void_p] * 7),
     "mxg_kuramoto_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                             c_int, c_void_p, c_void_p, c_void_p]),
+    "mxg_kuramoto_wide_render": (c_int, [c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mxg_atan_norm_host": (c_double, [c_double]),
     "mxg_shape_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mxg_xfade_render": (c_int, [c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

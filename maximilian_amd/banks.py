@@ -1688,11 +1688,13 @@ class maxiKuramotoBank(_Bank):
     the set's summed sines and cosines (N pairs per sample instead of N * N sines).  State: phase [S][N]; asynchronous sets
     also gathered [S][N] and update i32 [S].  dt is TWOPI / maxiSettings.sampleRate at each call.  set_phase / set_phases are
     the reference's setPhase / setPhases between two blocks; on asynchronous sets they raise the set's flag."""
+    MAX_N = KURAMOTO_MAX_N
+    ENTRY = "mxg_kuramoto_render"
 
     def __init__(self, sets, N, meanfield=False, asynchronous=False, stream=None):
         self.S, self.N = int(sets), int(N)
-        if not 1 <= self.N <= KURAMOTO_MAX_N:   # (before the device is touched, as the entry point refuses it)
-            raise ValueError("N: a set has 1 .. %d oscillators, got %d" % (KURAMOTO_MAX_N, self.N))
+        if not 1 <= self.N <= self.MAX_N:   # (before the device is touched, as the entry point refuses it)
+            raise ValueError("N: a set has 1 .. %d oscillators, got %d" % (self.MAX_N, self.N))
         super().__init__(sets, stream)
         self.mode = (1 if meanfield else 0) | (2 if asynchronous else 0)
         self.asynchronous = bool(asynchronous)
@@ -1759,9 +1761,9 @@ class maxiKuramotoBank(_Bank):
         out = dict(out or {})
         shapes = {"mix": (B, self.S), "phases": (B, self.S, self.N)}
         res = {n: out[n] if n in out else DeviceBuffer(shapes[n], np.float64, zero=False) for n, b in KURAMOTO_WANT.items() if bits & b}
-        check(lib().mxg_kuramoto_render(self.mode, self.S, self.N, B, _ptr(f), fps, _ptr(k), kps, self.phase.ptr, _ptr(self.gathered),
-                                        _ptr(self.update), bits, _ptr(res.get("mix")), _ptr(res.get("phases")), self.stream),
-              "mxg_kuramoto_render")
+        check(getattr(lib(), self.ENTRY)(self.mode, self.S, self.N, B, _ptr(f), fps, _ptr(k), kps, self.phase.ptr, _ptr(self.gathered),
+                                         _ptr(self.update), bits, _ptr(res.get("mix")), _ptr(res.get("phases")), self.stream),
+              self.ENTRY)
         return res
 
     def play(self, freq, K, B=None, out=None):
@@ -1784,6 +1786,18 @@ class maxiKuramotoBank(_Bank):
                 raise ValueError("render_phases: B is needed when freq and K are per set")
         r = self.render(B, freq, K, ("mix", "phases"), out)
         return r["mix"], r["phases"]
+
+
+KURAMOTO_WIDE_MAX_N = 1024
+
+
+class maxiKuramotoWideBank(maxiKuramotoBank):
+    """maxiKuramotoBank for sets of N = 1 .. 1024 oscillators (mxg_kuramoto_wide_render, K26: one workgroup per set, one lane per
+    oscillator).  The same methods, state and modes; it pays from N = 65 on -- up to 64 maxiKuramotoBank packs several sets into
+    a wavefront and gives the same bits.  The exact form is N * N sines per set and sample: a set of 1024 is about a million, and
+    only meanfield=True (N sine / cosine pairs) brings a set that wide near real time."""
+    MAX_N = KURAMOTO_WIDE_MAX_N
+    ENTRY = "mxg_kuramoto_wide_render"
 
 
 SAMPLE_MODES = {"play": 0, "playOnce": 1, "playLoop": 2, "playUntil": 3, "playAtSpeed": 4,

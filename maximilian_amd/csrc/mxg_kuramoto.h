@@ -1,7 +1,8 @@
 // mxg_kuramoto.h -- maxiKuramotoOscillator::play (H:1640-1654), maxiKuramotoOscillatorSet::play (H:1714-1727) and
 // maxiAsyncKuramotoOscillator::play (H:1775-1792) as plain arithmetic over one set's phases.  H = src/maximilian.h.  No device
-// state: the same text compiles for the host (tests/host_kuramoto.cpp) and for kernel K17 (kuramoto.hip), and the two agree
-// bit for bit.
+// state: the same text compiles for the host (tests/host_kuramoto.cpp, tests/host_kuramoto_wide.cpp) and for the kernels K17
+// (kuramoto.hip: sets of up to 64, several to a wavefront) and K26 (kuramoto_wide.hip: up to 1024, a workgroup each), and host
+// and device agree bit for bit.
 //
 // Per set and sample the reference gathers phases[j] = oscs[j].phase, then for every oscillator i, in order,
 //     adj = 0; for j: adj += sin(phases[j] - phase_i);                      (sequential in j)
@@ -41,6 +42,7 @@
 #define MXG_KURA_WANT_MIX 1
 #define MXG_KURA_WANT_PHASES 2
 #define MXG_KURA_MAX_N 64
+#define MXG_KURA_WIDE_MAX_N 1024  // kuramoto_wide.hip (K26): one workgroup per set
 
 namespace mxg {
 namespace {
@@ -179,6 +181,18 @@ __device__ __forceinline__ double kura_adj_meanfield(const double *sj, const dou
     }
     return ci * S - si * C;
 }
+
+// The same sum in two steps, for a kernel in which one lane forms S and C and every lane of the set reads them (kernel K26):
+// exactly what kura_adj_meanfield gives -- j order, from 0.0.
+__device__ __forceinline__ void kura_meanfield_sums(const double *sj, const double *cj, int N, double &S, double &C) {
+    S = 0.0;
+    C = 0.0;
+    for (int j = 0; j < N; j++) {
+        S += sj[j];
+        C += cj[j];
+    }
+}
+__device__ __forceinline__ double kura_meanfield_adj(double si, double ci, double S, double C) { return ci * S - si * C; }
 
 // the update line and the one wrap; returns what the oscillator's play() returns
 __device__ __forceinline__ double kura_advance(double phase, double dt, double freq, double K, int N, double adj) {
