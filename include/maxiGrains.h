@@ -1,6 +1,8 @@
 // include/maxiGrains.h -- DROP-IN for the reference's granular classes (src/libs/maxiGrains.h): maxiTimeStretch<F>,
 // maxiPitchShift<F>, maxiStretch<F> with the reference's window functor names as template parameters, one call per sample,
-// executed through the C-ABI's granular renderer (mxg_granular_render, include/maxigpu.h; kernels K8 .. K8d).
+// executed through the C-ABI's granular renderer (mxg_granular_render, include/maxigpu.h; kernels K8 .. K8d).  A maxiStretch whose loop
+// is not the whole sample, and every maxiStretch::playAtPosition call, goes through mxg_granular_pool_render (K27) with the object's
+// own sample as a pool of one slot; a maxiStretch with the default loop keeps the path and the launch count it always had.
 //
 // How a per-sample `ts->play(speed, grainLength, overlaps, posMod)` is served.  A stream (one object) is a scheduler -- position,
 // looper / cycles, randomOffset (L/maxiGrains.h:341-355, 412-430, 512-530) -- plus at most eight live grains; both live on the host
@@ -30,7 +32,8 @@ struct gaussianWinFunctor { static constexpr int kind = 8; };
 namespace maxigpu {
 namespace ps {
 
-// one granular stream behind the C-ABI: MODE 0 maxiTimeStretch::play, 1 maxiStretch::play, 2 playAtPosition, 3 maxiPitchShift::play
+// one granular stream behind the C-ABI: MODE 0 maxiTimeStretch::play, 1 maxiStretch::play, 2 playAtPosition, 3 maxiPitchShift::play,
+// 4 maxiStretch::playAtPosition (a = pitchstretch, b = pos)
 class GrainStream {
 public:
     GrainStream(int window_kind) : kind_(window_kind) {}
@@ -46,6 +49,15 @@ public:
         drop_block();
     }
     maxiSample *sample() const { return sample_; }
+    // maxiStretch's loop points in samples (L/maxiGrains.h:445).  Anything but (0, len) takes the pool renderer; a loop the reference
+    // could not survive -- loopStart >= loopEnd, where its unsigned loopLength wraps, or loopEnd > len -- is refused: silence.
+    void setLoop(unsigned long loopStart, unsigned long loopEnd) {
+        if (loopStart == ls_ && loopEnd == le_ && loop_set_) return;
+        settle();
+        ls_ = loopStart;
+        le_ = loopEnd;
+        loop_set_ = true;
+    }
     // scheduler members (host-authoritative between launches)
     double &position() { settle(); return st_[0]; }
     double &looper() { settle(); return st_[1]; }
@@ -78,7 +90,9 @@ private:
     Call sig_;
     bool spawn_at_end_ = false;  // the block's last sample is a spawn of mode 0 / 1: its rand() is drawn when that call is served
     double *d_ = nullptr;        // device scratch: [st 4][gst 32][par 3][out kMaxBlock] + int32 rnd
-    static constexpr size_t kDoubles = 4 + 32 + 3 + kMaxBlock + 2;
+    static constexpr size_t kDoubles = 4 + 32 + 3 + kMaxBlock + 2 + 4;  // (+ uint64 len, loopStart, loopEnd of the pool renderer)
+    unsigned long ls_ = 0, le_ = 0;  // maxiStretch's loop
+    bool loop_set_ = false;
 
     mxg_grain_plan *plan(double grainLength) {
         MAXIGPU_TRY {
@@ -100,7 +114,7 @@ private:
     }
     // samples until (and including) the next spawn of modes 0 / 1, counted with the scheduler's own additions (:343, :515: looper++)
     size_t next_len(const Call &c) const {
-        if (c.method != 0 && c.method != 1) return c.method == 2 ? 1 : kMaxBlock;  // playAtPosition: its position argument is a signal
+        if (c.method != 0 && c.method != 1) return (c.method == 2 || c.method == 4) ? 1 : kMaxBlock;  // playAtPosition: its position argument is a signal
         const double cycleLength = c.a[2] * maxiSettings::sampleRate / (int)c.a[3];  // :346 / :518
         const double thr = cycleLength + st_[2];
         double l = st_[1];
@@ -129,9 +143,25 @@ private:
         bool ok = check(mxg_memcpy_h2d(d_, h, sizeof(h), nullptr), "h2d grain state");
         ok = check(mxg_memcpy_h2d(d_rnd, &zero, sizeof(zero), nullptr), "h2d grain draw") && ok;
         const int mode = sig_.method;
+        const size_t len = sample_->getLength();
+        const bool looped = mode == 1 && loop_set_ && !(ls_ == 0 && le_ == len);
+        if (mode == 4 || looped) {  // K27 on the object's own sample as a pool of one slot (d_slot NULL: stream 0 reads slot 0)
+            if (looped && !(ls_ < le_ && le_ <= len)) {
+                maxigpu::ps::complain("maxiStretch: loopStart >= loopEnd or loopEnd > len is refused (INTEGRATION.md section 4): this call returns silence");
+                abandon();
+                return;
+            }
+            uint64_t *d_u = reinterpret_cast<uint64_t *>(d_ + 39 + kMaxBlock + 2);
+            const uint64_t hu[3] = {(uint64_t)len, (uint64_t)ls_, (uint64_t)le_};
+            ok = check(mxg_memcpy_h2d(d_u, hu, sizeof(hu), nullptr), "h2d grain loop") && ok;
+            ok = check(mxg_granular_pool_render(plan(sig_.a[2]), mode, 1, L, sample_->deviceSamples(), 0, len, 1, d_u, nullptr,
+                                                mode == 1 ? d_u + 1 : nullptr, (int)sig_.a[3], d_par, d_par + 1, mode == 1 ? d_par + 2 : nullptr, 0,
+                                                mode == 1 ? d_rnd : nullptr, 1, d_st, d_gst, d_out, nullptr), "mxg_granular_pool_render") && ok;
+        } else {
         ok = check(mxg_granular_render(plan(sig_.a[2]), mode, 1, L, sample_->deviceSamples(), sample_->getLength(), (int)sig_.a[3], d_par,
                                        mode == 1 ? d_par + 1 : nullptr, mode == 2 ? nullptr : d_par + 2, (mode == 0 || mode == 1) ? d_rnd : nullptr,
                                        1, d_st, d_gst, d_out, nullptr), "mxg_granular_render") && ok;
+        }
         double back[36] = {0};
         blk_.assign(L, 0.0);
         ok = check(mxg_memcpy_d2h(back, d_, sizeof(back), nullptr), "d2h grain state") && ok;  // (synchronises; reports a deferred render error)
@@ -226,18 +256,28 @@ public:
     size_t launches() const { return g_.launches; }
 };
 
-// ---- maxiStretch<F> (L/maxiGrains.h:437-542), the default loop (the whole sample) --------------------------------------------
+// ---- maxiStretch<F> (L/maxiGrains.h:437-542) ------------------------------------------------------------------------------
 template <typename F>
 class maxiStretch {
     maxigpu::ps::GrainStream g_{F::kind};
+    void wholeLoop() {  // ctor :456-464, setSample :473-475
+        loopStart = 0;
+        loopEnd = sample ? (unsigned long)sample->getLength() : 0;
+        loopLength = loopEnd;
+    }
 
 public:
     maxiSample *sample = nullptr;
+    unsigned long loopStart = 0, loopEnd = 0, loopLength = 0;  // :445
     maxiStretch() {}
-    maxiStretch(maxiSample *sample_) : sample(sample_) { g_.setSample(sample_); }
+    maxiStretch(maxiSample *sample_) : sample(sample_) {
+        g_.setSample(sample_);
+        wholeLoop();
+    }
     void setSample(maxiSample *newSample) {
         sample = newSample;
         g_.setSample(newSample);
+        wholeLoop();
         g_.position() = 0;
         g_.looper() = 0;
     }
@@ -247,10 +287,22 @@ public:
         double p = pos * sample->getLength();
         g_.position() = maxiMap::clamp(p, 0, sample->getLength() - 1);
     }
-    unsigned long getLoopEnd() { return sample ? (unsigned long)sample->getLength() : 0; }
+    void setLoopStart(double val) {  // :493-496
+        loopStart = val * sample->getLength();
+        loopLength = loopEnd - loopStart;
+    }
+    void setLoopEnd(double val) {  // :498-501
+        loopEnd = val * sample->getLength();
+        loopLength = loopEnd - loopStart;
+    }
+    unsigned long getLoopEnd() { return loopEnd; }
     inline double play(double pitchstretch = 1, double timestretch = 1, double grainLength = 0.05, int overlaps = 2, double posMod = 0.0) {
         if (sample == nullptr) return 0;  // :513
+        g_.setLoop(loopStart, loopEnd);
         return g_.play(1, pitchstretch, timestretch, grainLength, overlaps, posMod);
+    }
+    inline double playAtPosition(double pitchstretch = 1, double pos = 0, double grainLength = 0.05, int overlaps = 2) {  // :531-539
+        return g_.play(4, pitchstretch, pos, grainLength, overlaps, 0.0);
     }
     size_t launches() const { return g_.launches; }
 };

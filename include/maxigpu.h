@@ -173,7 +173,8 @@ int mxg_prof_overhead_ms(void *stream, int pairs, double *h_ms);
  * at the store-bound bank sizes whose whole grid is resident at once (45 056 ... 262 144 voices; mode B to 131 072, the mixdown form to 65 536); 1 never; >= 2 a fixed P; timing only, same bits), "osc_pace" (the same for mxg_osc_render: 0 automatic = the table-free waveforms at 90 112 ... 327 680 voices; 1 never; >= 2 a fixed P),
  * "tab_sides" (mxg_osc_render_tables*: 0 automatic = 1 workgroups of 256 lanes, one round of 8 voices at a time, two per CU; 2 = workgroups of 512 lanes, two rounds side by side),
  * "smp_pace" (the paced schedule for mxg_sample_render: 0 automatic = play() at 45 056 ... 229 375 voices; 1 never; >= 2 a fixed P), "smp_ring" (the *AtSpeed players' window rows as rings: 0 automatic = samples beyond 1 GiB, 1 off, 2 on), "grain_spin_limit" (see mxg_granular_retries), "osc_xcd" (workgroups renumbered so that each of the eight XCDs renders
- * one contiguous eighth of the bank: 0 automatic, 1 off, 2 on), "grain_sync" (mxg_granular_render reads its error word back before it returns, 0|1;
+ * one contiguous eighth of the bank: 0 automatic, 1 off, 2 on), "grain_pool_tiles" (mxg_granular_pool_render: 0 automatic = the scheduler pass + tile
+ * render for calls of at least 128 samples, 1 = the one-lane-per-stream walk only, 2 = the tile form wherever it can run), "grain_sync" (mxg_granular_render reads its error word back before it returns, 0|1;
  * default 0: deferred, see mxg_last_async_error), "part_spin_limit" (polls a time-split kernel's writer part makes before it gives up
  * and reports through mxg_last_async_error), "part_fault" (test-only fault injection: that writer waits for a signal that never comes).
  * "rw_chunk" (samples per chunk of the pair-row maxiFilter kernel / rows per chunk of the noise column walk: 0 automatic = 8, 4 / 8 / 16 / 32;
@@ -1351,6 +1352,40 @@ int mxg_granular_render_mix(const mxg_grain_plan *plan, int mode, size_t S, size
                             size_t len, int overlaps, const double *d_a, const double *d_b,
                             const double *d_posmod, const int32_t *d_rnd, size_t R, double *d_st, double *d_gst,
                             double *d_out, const double *d_pan, double *d_mix, void *stream);
+
+/* ---- granular streams over the slots of a sample pool (K27, csrc/grainpool.hip, csrc/mxg_grainpool.h) ------------------------
+ * S streams that each read their OWN slot: the reference's maxiTimeStretch / maxiPitchShift / maxiStretch objects after
+ * setSample(), maxiStretch with its loop points (L/maxiGrains.h:445, :493-509, :514-517) and maxiStretch::playAtPosition
+ * (:531-539).  The pool is the one of mxg_sample_pool_alloc (slot r = d_pool + r * stride, d_len [R]; a length above cap is read as
+ * cap); a pointer from mxg_sample_upload with R = 1, stride = 0 and a one-element d_len is a valid pool too.
+ *   mode     0 ... 3 as mxg_granular_render; 4 = maxiStretch::playAtPosition(pitchstretch = a, pos = b, grainLength, overlaps).
+ *   d_slot   uint32 [S]: the slot each stream reads; NULL: stream s reads slot s (needs S <= R).  An index >= R is refused before
+ *            anything is launched: the S indices are read back, which is this entry point's one wait (NULL: none).
+ *   d_loop   uint64 [2][S]: loopStart | loopEnd in samples (mxg_stretch_loop_host makes them); NULL: 0 and len.  Mode 1 only.
+ *   d_a      modes 0 / 3 speed, 1 / 4 pitchstretch: [S], or [T][S] under MXG_GPOOL_PS_A; mode 2: the position signal [T][S].
+ *   d_b      mode 1 timestretch, mode 4 the position: [S], or [T][S] under MXG_GPOOL_PS_B.
+ *   d_posmod modes 0 / 1 / 3: NULL, [S], or [T][S] under MXG_GPOOL_PS_POSMOD.
+ * A per-sample value is the argument a patch hands play() in that sample: speed / rate move `position` at every sample, a grain
+ * takes the values of the sample it is born in.  d_rnd [S][Rn], d_st [4][S], d_gst [4][8][S] and d_out [T][S] mean what they mean in
+ * mxg_granular_render (a carried grain is checked against the stream's own slot length), and what the device finds while it renders
+ * is reported the same way, through mxg_last_async_error.  A stream whose slot is empty reads nothing, keeps its state and is
+ * silent (reported as a step its reads could not survive).  BIT-EXACT, and independent of how T is split into calls; with one
+ * slot, d_loop = NULL and ps_flags = 0, modes 0 ... 3 give the output and state of mxg_granular_render on the same sample.
+ * mxg_granular_pool_host: the same text on host arrays in the pool's layout, no device touched; a failure of a stream is its
+ * status.  mxg_stretch_loop_host: setLoopStart / setLoopEnd's conversions (unsigned long)(val * len); NaN, a negative value,
+ * loopStart >= loopEnd (where the reference's unsigned loopLength wraps: INTEGRATION.md section 4) and loopEnd > len are refused. */
+#define MXG_GPOOL_PS_A 1
+#define MXG_GPOOL_PS_B 2
+#define MXG_GPOOL_PS_POSMOD 4
+int mxg_granular_pool_render(const mxg_grain_plan *plan, int mode, size_t S, size_t T, const double *d_pool, size_t stride, size_t cap,
+                             size_t R, const uint64_t *d_len, const uint32_t *d_slot, const uint64_t *d_loop, int overlaps,
+                             const double *d_a, const double *d_b, const double *d_posmod, int ps_flags, const int32_t *d_rnd, size_t Rn,
+                             double *d_st, double *d_gst, double *d_out, void *stream);
+int mxg_granular_pool_host(const mxg_grain_plan *plan, int mode, size_t S, size_t T, const double *h_pool, size_t stride, size_t cap,
+                           size_t R, const uint64_t *h_len, const uint32_t *h_slot, const uint64_t *h_loop, int overlaps,
+                           const double *h_a, const double *h_b, const double *h_posmod, int ps_flags, const int32_t *h_rnd, size_t Rn,
+                           double *h_st, double *h_gst, double *h_out);
+int mxg_stretch_loop_host(uint64_t len, double start01, double end01, uint64_t *loopStart, uint64_t *loopEnd);
 
 /* ---- multi-GPU mixdown: RCCL over xGMI ------------------------------------------------ */
 /* The reference is single-device; there is nothing to cite but the mix itself (maxiMix, C:503-541, and the user-side

@@ -1346,6 +1346,7 @@ public:
     size_t capacity() const { return cap_; }
     size_t stride() const { return stride_; }
     double *deviceSamples(size_t r) const { return pool_ + r * stride_; }
+    const uint64_t *deviceLengths() const { return d_len_.get(); }  // uint64 [R] on the device (mxg_granular_pool_render's d_len)
     size_t getLength(size_t r) const { return (size_t)len_[r]; }
     // maxiSample::setSample (H:670-678) on one slot: the data, zeros up to the capacity, position = len - 1
     void setSample(size_t r, const std::vector<double> &data) {
@@ -1421,6 +1422,185 @@ private:
     maxigpu::DeviceArray<uint64_t> d_len_;
     maxigpu::DeviceArray<uint32_t> d_dropped_;
     maxigpu::DeviceArray<double> d_recpos_, d_lag_, d_position_, d_mix_, d_start_, d_end_, d_pstart_, d_pend_, d_level_;
+};
+
+// S granular streams that each read their OWN slot of a maxiLooperBank's pool (K27, mxg_granular_pool_render): the reference's
+// maxiTimeStretch / maxiPitchShift / maxiStretch objects after setSample(), maxiStretch with its loop points (L/maxiGrains.h:445,
+// :493-509) and playAtPosition (:531-539).  A parameter is [S] on the device, or a block [N][S] another bank wrote (perSample = true):
+// a block is read at every sample.  Every render writes the [N][S] block maxiMixBank::stereo takes.  Bit-exact, and independent of
+// how the samples are split into calls.  A render only enqueues while stream s reads slot s; with any other assignment the C-ABI reads
+// the slot indices back before it launches, so the call waits for the stream.  The bank must not outlive its pool.
+class maxiGrainPoolBank {
+public:
+    maxiGrainPoolBank(size_t streams, const maxiLooperBank &pool, int window_kind = 0)
+        : S(streams), pool_(pool), kind_(window_kind), slot_(streams), loop_(2 * streams), whole_(streams, 1) {
+        maxigpu::check(mxg_init(-1), "mxg_init");
+        d_st_.resize(4 * S);
+        d_gst_.resize(32 * S);
+        d_slot_.resize(S);
+        d_loop_.resize(2 * S);
+        for (size_t s = 0; s < S; s++) {
+            slot_[s] = (uint32_t)(s % pool_.slots());
+            loop_[s] = 0;
+            loop_[S + s] = pool_.getLength(slot_[s]);
+        }
+    }
+    maxiGrainPoolBank(const maxiGrainPoolBank &) = delete;
+    maxiGrainPoolBank &operator=(const maxiGrainPoolBank &) = delete;
+    ~maxiGrainPoolBank() {
+        for (auto &p : plans_) mxg_grain_plan_destroy(p.second);
+    }
+    size_t streams() const { return S; }
+    size_t getLength(size_t s) const { return pool_.getLength(slot_[at(s)]); }
+    uint32_t getSlot(size_t s) const { return slot_[at(s)]; }
+    // setSample() of stream s: slot r from now on, no live grains; stretch = maxiStretch::setSample (:466-478): position, looper and
+    // the loop are reset too
+    void setSlot(size_t s, size_t r, bool stretch = true) {
+        if (s >= S || r >= pool_.slots()) throw std::invalid_argument("maxiGrainPoolBank::setSlot: the stream or the slot does not exist");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        slot_[s] = (uint32_t)r;
+        std::vector<double> g = d_gst_.download();
+        for (size_t i = 0; i < 32; i++) g[i * S + s] = 0.0;
+        d_gst_.upload(g);
+        if (stretch) {
+            std::vector<double> st = d_st_.download();
+            st[s] = st[S + s] = 0.0;
+            d_st_.upload(st);
+            loop_[s] = 0;
+            loop_[S + s] = pool_.getLength(r);
+            whole_[s] = 1;
+        }
+        dirty_ = true;
+    }
+    // setLoopStart + setLoopEnd (:493-501): NaN, a negative value, loopStart >= loopEnd and loopEnd > len are refused
+    void setLoop(size_t s, double start01, double end01) {
+        uint64_t ls = 0, le = 0;
+        maxigpu::check(mxg_stretch_loop_host(getLength(s), start01, end01, &ls, &le), "mxg_stretch_loop_host");
+        loop_[s] = ls;
+        loop_[S + s] = le;
+        whole_[s] = 0;
+        dirty_ = true;
+    }
+    void setLoopStart(size_t s, double val) {
+        uint64_t ls = 0, le = 0;
+        maxigpu::check(mxg_stretch_loop_host(getLength(s), val, 1.0, &ls, &le), "mxg_stretch_loop_host");
+        followLengths();
+        if (ls >= loop_[S + s]) throw std::invalid_argument("maxiGrainPoolBank::setLoopStart: loopStart >= loopEnd");
+        loop_[s] = ls;
+        whole_[s] = 0;
+        dirty_ = true;
+    }
+    void setLoopEnd(size_t s, double val) {
+        uint64_t ls = 0, le = 0;
+        maxigpu::check(mxg_stretch_loop_host(getLength(s), 0.0, val, &ls, &le), "mxg_stretch_loop_host");
+        if (le <= loop_[s]) throw std::invalid_argument("maxiGrainPoolBank::setLoopEnd: loopStart >= loopEnd");
+        loop_[S + s] = le;
+        whole_[s] = 0;
+        dirty_ = true;
+    }
+    unsigned long getLoopStart(size_t s) const { return (unsigned long)loop_[at(s)]; }
+    unsigned long getLoopEnd(size_t s) {
+        followLengths();
+        return (unsigned long)loop_[S + at(s)];
+    }
+    void setPosition(size_t s, double pos) {  // :488-491
+        at(s);
+        const double n = (double)getLength(s);
+        double p = pos * n;
+        p = p < 0.0 ? 0.0 : (p > n - 1.0 ? n - 1.0 : p);
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_st_.upload(&p, 1, s);
+    }
+    std::vector<double> getPosition() const {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        std::vector<double> st = d_st_.download();
+        st.resize(S);
+        return st;
+    }
+    std::vector<double> getNormalisedPosition() const {
+        std::vector<double> p = getPosition();
+        for (size_t s = 0; s < S; s++) p[s] /= (double)getLength(s);
+        return p;
+    }
+    std::vector<double> state() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_st_.download(); }    // [4][S]
+    std::vector<double> grains() const { maxigpu::check(mxg_sync(), "mxg_sync"); return d_gst_.download(); }  // [4][8][S]
+    // maxiTimeStretch::play (:341-355); d_rnd int32 [S][Rn] or null
+    void timestretch(size_t N, const double *d_speed, bool perSample, double grainLength, int overlaps, const double *d_posMod, bool posModPerSample,
+                     const int32_t *d_rnd, size_t Rn, double *d_out, void *stream = nullptr) {
+        render(0, N, d_speed, perSample, nullptr, false, grainLength, overlaps, d_posMod, posModPerSample, d_rnd, Rn, d_out, stream);
+    }
+    // maxiPitchShift::play (:412-430)
+    void pitchshift(size_t N, const double *d_speed, bool perSample, double grainLength, int overlaps, const double *d_posMod, bool posModPerSample,
+                    double *d_out, void *stream = nullptr) {
+        render(3, N, d_speed, perSample, nullptr, false, grainLength, overlaps, d_posMod, posModPerSample, nullptr, 0, d_out, stream);
+    }
+    // maxiStretch::play (:512-530) inside each stream's loop points
+    void stretch(size_t N, const double *d_pitch, bool pitchPerSample, const double *d_rate, bool ratePerSample, double grainLength, int overlaps,
+                 const double *d_posMod, bool posModPerSample, const int32_t *d_rnd, size_t Rn, double *d_out, void *stream = nullptr) {
+        render(1, N, d_pitch, pitchPerSample, d_rate, ratePerSample, grainLength, overlaps, d_posMod, posModPerSample, d_rnd, Rn, d_out, stream);
+    }
+    // maxiTimeStretch::playAtPosition (:359-367): d_pos [N][S]
+    void playAtPosition(size_t N, const double *d_pos, double grainLength, int overlaps, double *d_out, void *stream = nullptr) {
+        render(2, N, d_pos, false, nullptr, false, grainLength, overlaps, nullptr, false, nullptr, 0, d_out, stream);
+    }
+    // maxiStretch::playAtPosition (:531-539): d_pos [S], or [N][S] with posPerSample
+    void stretchAtPosition(size_t N, const double *d_pitch, bool pitchPerSample, const double *d_pos, bool posPerSample, double grainLength,
+                           int overlaps, double *d_out, void *stream = nullptr) {
+        render(4, N, d_pitch, pitchPerSample, d_pos, posPerSample, grainLength, overlaps, nullptr, false, nullptr, 0, d_out, stream);
+    }
+
+private:
+    size_t at(size_t s) const {
+        if (s >= S) throw std::out_of_range("maxiGrainPoolBank: the stream does not exist");
+        return s;
+    }
+    // a stream on its whole slot has loopEnd = the slot's length NOW (the pool's setSample / setLength may have changed it), as the
+    // reference's setSample re-derives it; a loop that was set stays as set
+    void followLengths() {
+        for (size_t s = 0; s < S; s++)
+            if (whole_[s] && loop_[S + s] != pool_.getLength(slot_[s])) {
+                loop_[S + s] = pool_.getLength(slot_[s]);
+                dirty_ = true;
+            }
+    }
+    mxg_grain_plan *plan(double grainLength) {
+        for (auto &p : plans_)
+            if (p.first == grainLength) return p.second;
+        mxg_grain_plan *pl = mxg_grain_plan_create(kind_, grainLength, 44100);  // maxiSample::setSample: mySampleRate = 44100 (H:676)
+        if (!pl) throw std::runtime_error(std::string("mxg_grain_plan_create: ") + mxg_last_error());
+        plans_.push_back(std::make_pair(grainLength, pl));
+        return pl;
+    }
+    void render(int mode, size_t N, const double *d_a, bool psA, const double *d_b, bool psB, double grainLength, int overlaps, const double *d_pm,
+                bool psP, const int32_t *d_rnd, size_t Rn, double *d_out, void *stream) {
+        followLengths();
+        if (dirty_) {
+            maxigpu::check(mxg_sync(), "mxg_sync");
+            d_slot_.upload(slot_);
+            d_loop_.upload(loop_);
+            dirty_ = false;
+        }
+        // the indices were checked in setSlot.  Stream s on slot s needs no d_slot, and then the call only enqueues; any other assignment
+        // hands the C-ABI the device array, which it reads back before it launches (that call waits for the stream)
+        bool identity = S <= pool_.slots();
+        for (size_t s = 0; identity && s < S; s++) identity = slot_[s] == s;
+        const int ps = (psA && mode != 2 ? MXG_GPOOL_PS_A : 0) | (psB ? MXG_GPOOL_PS_B : 0) | (psP && d_pm ? MXG_GPOOL_PS_POSMOD : 0);
+        maxigpu::check(mxg_granular_pool_render(plan(grainLength), mode, S, N, pool_.deviceSamples(0), pool_.stride(), pool_.capacity(), pool_.slots(),
+                                                pool_.deviceLengths(), identity ? nullptr : d_slot_.get(), mode == 1 ? d_loop_.get() : nullptr, overlaps, d_a, d_b, d_pm, ps,
+                                                d_rnd, Rn, d_st_.get(), d_gst_.get(), d_out, stream),
+                       "mxg_granular_pool_render");
+    }
+    size_t S;
+    const maxiLooperBank &pool_;
+    int kind_;
+    bool dirty_ = true;
+    std::vector<uint32_t> slot_;
+    std::vector<uint64_t> loop_;
+    std::vector<char> whole_;  // the stream's loop is its whole slot
+    std::vector<std::pair<double, mxg_grain_plan *>> plans_;
+    maxigpu::DeviceArray<uint32_t> d_slot_;
+    maxigpu::DeviceArray<uint64_t> d_loop_;
+    maxigpu::DeviceArray<double> d_st_, d_gst_;
 };
 
 // V x maxiMap / maxiConvert (mxg_map_render): stateless, flat over the block; d_out may be d_in.  Ranges are one value for the

@@ -20,4 +20,4 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import (maxiConvolve, maxiConvolveBank, maxiFFT, maxiIFFT, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
                        padded_stream)
-from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, WINDOWS  # noqa: F401
+from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, maxiGrainPoolBank, WINDOWS  # noqa: F401

@@ -237,6 +237,13 @@ SIGNATURES = {
     "mxg_granular_render_mix": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "mxg_granular_pool_render": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "mxg_granular_pool_host": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                       c_void_p]),
+    "mxg_stretch_loop_host": (c_int, [ctypes.c_uint64, c_double, c_double, c_void_p, c_void_p]),
     "mxg_comm_unique_id": (c_int, [c_void_p]),
     "mxg_comm_create": (c_void_p, [c_void_p, c_int, c_int]),
     "mxg_comm_destroy": (c_int, [c_void_p]),

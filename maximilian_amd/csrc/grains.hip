@@ -26,14 +26,7 @@
 #include "mxg_common.h"
 #include "mxg_sched.h"
 #include "mxg_lanefold.h"
-
-struct mxg_grain_plan {
-    int window_kind, mySampleRate;
-    double grainLength;
-    unsigned long sampleDur;
-    double *d_window;  // [sampleDur]
-    std::vector<double> h_window;
-};
+#include "mxg_grainplan.h"
 
 namespace mxg {
 namespace {

@@ -63,6 +63,7 @@ Tune g_tune[] = {
     {"mix_rows", 2, 1, 2},  // K3: sample rows per workgroup sharing one read of the gains (stereo, no bus output)
     {"fft_generic", 0, 0, 1},  // 1: force the generic per-stage FFT kernel also for fftSize 1024
     {"grain_chunked", 1, 0, 1},  // 0: serial-in-time K8 instead of the time-sharded K8a+K8b
+    {"grain_pool_tiles", 0, 0, 2},  // K27: 0 automatic, 1 the walk only, 2 the tile form wherever it can run
     {"grain_lanes_k", 128, 16, 4096},  // K8b: target number of (stream, chunk) lanes, in units of 1024
     {"grain_line", 1, 0, 1},  // K8d: tile render for arbitrary increments (0: the (stream, chunk) walk K8b)
     {"grain_unit", 1, 0, 1},  // K8c: coalesced closed-form render when every grain has inc = +-1
