@@ -1436,6 +1436,30 @@ int mxg_mixq_flush(mxg_mixq *q, void *stream);
 const double *mxg_mixq_result(const mxg_mixq *q, size_t *h_blocks, size_t *h_batches);
 int mxg_mixq_release(mxg_mixq *q, void *stream);
 
+/* ---- long signals of few voices, parallel in time (K28) ------------------------------------------------------------------
+ * mxg_scan_long_render: V voices (1 ... 4096) x N samples (1 ... 2^28) of a LINEAR filter with block-constant coefficients, the
+ * signal [N][V] cut into chunks of 2048 samples that are joined by a scan: three launches on `stream` (chunk summaries, the scan
+ * over the chunks, the render), no workgroup waiting on another.  V = 1 is a plain contiguous signal (a sample-pool slot, an
+ * uploaded maxiSample).  d_out == d_in is allowed; any other overlap of the two is refused.  Out-of-range V, N or kind: MXG_ERR_INVALID.
+ *   kind 0 maxiDCBlocker, 1 maxiSVF, 2 maxiBiquad   d_coef / d_st: mxg_filter2_render's [NC][V] / [3][V]
+ *   kind 3 lores, 4 hires                           d_coef: rows c, r of mxg_filter_coeffs_host; d_st: mxg_filter_render's [5][V],
+ *                                                   rows 0-1 read and written, rows 2-4 left as they are
+ *   kind 5 maxiLagExp                               d_coef [2][V] = alpha, alphaReciprocal; d_st [1][V] = val (mxg_lag_render's d_val)
+ * One state array can alternate between this entry point and the sequential one of its kind.  The knob time_parallel plays no part.
+ * The arithmetic is REORDERED (a state reaches a chunk through matrix products): a TOLERANCE mode.  |error| <= SCAN_LONG_RTOL x the
+ * voice's peak of the sequential output, for stable settings and finite input over the whole parameter domain and a stream of up to
+ * 2.5e7 samples per voice carried from a state; per kind, measured on the host twin (worst over N = 2, 65 and 4097 chunks and a ragged N,
+ * three carried calls, the whole sweep at 4097 chunks among them) -> the bound (worst x 2, one digit, rounded up):
+ *     maxiDCBlocker 2.3e-12 -> 5e-12    maxiSVF 3.5e-10 -> 8e-10    maxiBiquad 1.6e-10 -> 4e-10 (the sequential recurrence is itself
+ *     lores 7.6e-13 -> 2e-12            hires 7.4e-13 -> 2e-12      maxiLagExp 4.1e-12 -> 9e-12  1.3e-10 from a long-double one there)
+ * The worst cases are the settings that barely decay.  An UNDAMPED maxiSVF (res 0, |pole| = 1) is the one whose error keeps growing
+ * with the length of the stream -- 5.1e-11 after 8.4e6 samples, 3.3e-10 after 2.5e7 at 15 kHz -- and beyond that length its bound does
+ * not hold (tests/test_scan_long_host.py has the table).
+ * After a NaN / Inf input sample the outputs and states are non-finite where the sequential recurrence's are; NaN and Inf may
+ * trade places.  mxg_scan_long_host: the same arithmetic on host arrays -- the device gives these bits. */
+int mxg_scan_long_render(int kind, size_t V, size_t N, const double *d_in, const double *d_coef, double *d_st, double *d_out, void *stream);
+int mxg_scan_long_host(int kind, size_t V, size_t N, const double *h_in, const double *h_coef, double *h_st, double *h_out);
+
 /* (The bandwidth-probe kernels bench.py and tools/ measure ceilings with are NOT part of this ABI: include/maxicalib.h,
  * libmaxicalib.so -- measurement code, built beside the product library.) */
 

@@ -2478,3 +2478,85 @@ private:
         dst_ = d_dst_.download(); ist_ = d_ist_.download();
     }
 };
+
+// V (1 ... 4096) linear filters with block-constant coefficients over LONG signals, parallel in time (mxg_scan_long_render, K28):
+// maxiDCBlocker, maxiSVF, maxiBiquad, maxiFilter::lores / hires or maxiLagExp, the signal [N][V] cut into chunks of 2048 samples
+// that a scan joins.  A tolerance mode (maxigpu.h: SCAN_LONG_RTOL per kind), not bit-exact against the sequential banks.  The state
+// rows are those of the sequential entry point of the kind ([3][V], [5][V] or [1][V]): state() / set_state() hand a stream over to
+// one and back.  V = 1 filters a plain contiguous signal, e.g. maxiLooperBank::deviceSamples(r); d_out == d_in is allowed.
+class maxiLongScanBank {
+public:
+    enum Kind { DC = 0, SVF = 1, BIQUAD = 2, LORES = 3, HIRES = 4, LAG = 5 };
+    maxiLongScanBank(size_t voices, Kind kind) : V(voices), kind_(kind) {
+        maxigpu::check(mxg_init(-1), "mxg_init");
+        d_st_.resize(state_rows() * V);
+    }
+    size_t voices() const { return V; }
+    Kind kind() const { return kind_; }
+    size_t coef_rows() const { return kind_ == DC ? 1 : kind_ == SVF ? 9 : kind_ == BIQUAD ? 5 : 2; }
+    size_t state_rows() const { return kind_ <= BIQUAD ? 3 : kind_ == LAG ? 1 : 5; }
+    void setDC(const std::vector<double> &R) { set(DC, need(R)); }
+    void setSVF(const std::vector<double> &cutoff, const std::vector<double> &res, double lp, double bp, double hp, double notch) {
+        std::vector<double> c(9 * V);
+        maxigpu::check(mxg_svf_coeffs_host(V, need(cutoff).data(), need(res).data(), c.data()), "mxg_svf_coeffs_host");
+        const double mix[4] = {lp, bp, hp, notch};
+        for (size_t r = 0; r < 4; r++)
+            for (size_t v = 0; v < V; v++) c[(5 + r) * V + v] = mix[r];
+        set(SVF, c);
+    }
+    void setBiquad(const std::vector<int32_t> &type, const std::vector<double> &cutoff, const std::vector<double> &Q, const std::vector<double> &peakGain) {
+        if (type.size() != V) throw std::invalid_argument("maxiLongScanBank: one value per voice");
+        std::vector<double> c(5 * V);
+        maxigpu::check(mxg_biquad_coeffs_host(V, type.data(), need(cutoff).data(), need(Q).data(), need(peakGain).data(), c.data()), "mxg_biquad_coeffs_host");
+        set(BIQUAD, c);
+    }
+    void setLores(const std::vector<double> &cutoff, const std::vector<double> &res) { set(LORES, cr(cutoff, res)); }
+    void setHires(const std::vector<double> &cutoff, const std::vector<double> &res) { set(HIRES, cr(cutoff, res)); }
+    void setLag(const std::vector<double> &alpha) {  // maxiLagExp::init: alphaReciprocal = 1 - alpha
+        std::vector<double> c(need(alpha));
+        for (size_t v = 0; v < V; v++) c.push_back(1.0 - alpha[v]);
+        set(LAG, c);
+    }
+    const std::vector<double> &coefficients() const { return coef_; }
+    // N samples per voice, d_in / d_out [N][V] on the device
+    void process(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        if (coef_.empty()) throw std::logic_error("maxiLongScanBank: no coefficients set");
+        maxigpu::check(mxg_scan_long_render((int)kind_, V, N, d_in, d_coef_.get(), d_st_.get(), d_out, stream), "mxg_scan_long_render");
+    }
+    // the host twin (the device's bits) on host arrays from the state `st` [state_rows()][V], which it advances
+    void host(size_t N, const double *h_in, double *h_out, std::vector<double> &st) const {
+        if (coef_.empty() || st.size() != state_rows() * V) throw std::logic_error("maxiLongScanBank::host: coefficients and a whole state array");
+        maxigpu::check(mxg_scan_long_host((int)kind_, V, N, h_in, coef_.data(), st.data(), h_out), "mxg_scan_long_host");
+    }
+    std::vector<double> state() const {
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        return d_st_.download();
+    }
+    void set_state(const std::vector<double> &st) {
+        if (st.size() != state_rows() * V) throw std::invalid_argument("maxiLongScanBank::set_state: [state_rows()][V] values");
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_st_.upload(st);
+    }
+
+private:
+    const std::vector<double> &need(const std::vector<double> &a) const {
+        if (a.size() != V) throw std::invalid_argument("maxiLongScanBank: one value per voice");
+        return a;
+    }
+    std::vector<double> cr(const std::vector<double> &cutoff, const std::vector<double> &res) const {
+        std::vector<double> c(3 * V);
+        maxigpu::check(mxg_filter_coeffs_host(0, V, need(cutoff).data(), need(res).data(), c.data()), "mxg_filter_coeffs_host");  // (lores and hires share c, r)
+        c.resize(2 * V);
+        return c;
+    }
+    void set(Kind k, const std::vector<double> &c) {
+        if (k != kind_) throw std::logic_error("maxiLongScanBank: this setter is of another kind");
+        coef_ = c;
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        d_coef_.upload(coef_);
+    }
+    size_t V;
+    Kind kind_;
+    std::vector<double> coef_;
+    maxigpu::DeviceArray<double> d_coef_, d_st_;
+};

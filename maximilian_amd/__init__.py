@@ -16,7 +16,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiDynBank, maxiEnvelopeBank, maxiLagExpBank, maxiMapBank, dyn_coeff, dyn_makeup, MAP_MODES, CLASSIC_PS,
                     maxiPolyBLEPBank, polyblep_sync, POLYBLEP_WAVEFORMS,
                     maxiKickBank, maxiSnareBank, maxiHatsBank, maxiClockBank, DRUM_KINDS,
-                    maxiAtomBank, ATOM_KINDS, ATOM_ONSETS, maxiLooperBank, LOOPER_PLAY,
+                    maxiAtomBank, ATOM_KINDS, ATOM_ONSETS, maxiLooperBank, LOOPER_PLAY, maxiLongScanBank, LONG_SCAN_KINDS,
                     FILTER_KINDS, SAMPLE_MODES)
 from .spectral import (maxiConvolve, maxiConvolveBank, maxiFFT, maxiIFFT, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
                        padded_stream)

@@ -2499,3 +2499,118 @@ class maxiLooperBank(_Bank):
             self.free()
         except Exception:
             pass
+
+
+LONG_SCAN_KINDS = {"dc": 0, "svf": 1, "biquad": 2, "lores": 3, "hires": 4, "lag": 5}
+_LONG_SCAN_ROWS = {0: (1, 3), 1: (9, 3), 2: (5, 3), 3: (2, 5), 4: (2, 5), 5: (2, 1)}   # kind: (coefficient rows, state rows)
+
+
+class maxiLongScanBank:
+    """V (1 ... 4096) linear filters with block-constant coefficients over LONG signals, parallel in time (mxg_scan_long_render,
+    K28): maxiDCBlocker, maxiSVF, maxiBiquad, maxiFilter::lores / hires or maxiLagExp, the signal [N][V] cut into chunks of 2048
+    samples that a scan joins.  A tolerance mode (include/maxigpu.h: SCAN_LONG_RTOL per kind), not bit-exact against the
+    sequential banks; the state rows are those of the sequential bank of the kind ([3][V], [5][V] or [1][V]), so set_state() /
+    state() hand a stream over to one and back.  V = 1 filters a plain contiguous signal: a maxiLooperBank slot_pointer, an uploaded
+    maxiSample.  The device is first touched by process(); the setters, state() before it and host() need none."""
+
+    def __init__(self, voices, kind, stream=None):
+        self.V = int(voices)
+        self.kind = LONG_SCAN_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if self.kind not in _LONG_SCAN_ROWS:
+            raise ValueError("maxiLongScanBank: kind %r is none of %s" % (kind, sorted(LONG_SCAN_KINDS)))
+        self.stream = stream
+        self.NC, self.NS = _LONG_SCAN_ROWS[self.kind]
+        self.coef = None                      # host [NC][V]
+        self._st = np.zeros((self.NS, self.V))
+        self._dcoef = self._dst = None
+
+    def _rows(self, *a):
+        return [np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), (self.V,))) for x in a]
+
+    def _set(self, kinds, coef):
+        if self.kind not in kinds:
+            raise ValueError("maxiLongScanBank: this setter is not of kind %d" % self.kind)
+        self.coef = np.ascontiguousarray(coef, np.float64).reshape(self.NC, self.V)
+        self._dcoef = None
+
+    def setDC(self, R):
+        self._set((0,), np.stack(self._rows(R)))
+
+    def setSVF(self, cutoff, res, mixes):
+        """maxiSVF::setCutoff / setResonance and the four mixes of play(w, lp, bp, hp, notch)."""
+        cu, rs = self._rows(cutoff, res)
+        c = np.zeros((5, self.V))
+        check(lib().mxg_svf_coeffs_host(self.V, cu.ctypes.data, rs.ctypes.data, c.ctypes.data), "mxg_svf_coeffs_host")
+        self._set((1,), np.concatenate([c, np.stack(self._rows(*mixes))]))
+
+    def setBiquad(self, filtType, cutoff, Q, peakGain):
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(filtType, np.int32), (self.V,)))
+        cu, q, g = self._rows(cutoff, Q, peakGain)
+        c = np.zeros((5, self.V))
+        check(lib().mxg_biquad_coeffs_host(self.V, t.ctypes.data, cu.ctypes.data, q.ctypes.data, g.ctypes.data, c.ctypes.data), "mxg_biquad_coeffs_host")
+        self._set((2,), c)
+
+    def setLores(self, cutoff, res):
+        cu, rs = self._rows(cutoff, res)
+        self._set((3,), filter_coeffs(0, cu, rs)[:2])
+
+    def setHires(self, cutoff, res):
+        cu, rs = self._rows(cutoff, res)
+        self._set((4,), filter_coeffs(0, cu, rs)[:2])   # (lores and hires share c and r, C:456-461 / C:471-476)
+
+    def setLag(self, alpha, alphaReciprocal=None):
+        """maxiLagExp::init: alphaReciprocal = 1 - alpha unless given (the reference keeps the two independent)."""
+        a, = self._rows(alpha)
+        r = 1.0 - a if alphaReciprocal is None else self._rows(alphaReciprocal)[0]
+        self._set((5,), np.stack([a, r]))
+
+    def state(self):
+        if self._dst is not None:
+            self._st = self._dst.numpy()
+        return self._st.copy()
+
+    def set_state(self, st):
+        self._st = np.ascontiguousarray(np.broadcast_to(np.asarray(st, np.float64), (self.NS, self.V))).copy()
+        if self._dst is not None:
+            self._dst.upload(self._st)
+
+    def _need_coef(self):
+        if self.coef is None:
+            raise ValueError("maxiLongScanBank: no coefficients set")
+
+    def process(self, x, N=None, out=None):
+        """x: numpy [N][V] (uploaded), a DeviceBuffer / torch tensor [N][V], or a raw device address with N.  out: None (a new
+        DeviceBuffer), the same kinds of device object, or x itself for in place.  Returns out."""
+        self._need_coef()
+        check(lib().mxg_init(-1), "mxg_init")
+        if isinstance(x, np.ndarray):
+            a = np.ascontiguousarray(x, np.float64).reshape(-1, self.V)
+            x = DeviceBuffer.from_numpy(a)
+        if N is None:
+            if not hasattr(x, "shape"):
+                raise ValueError("maxiLongScanBank.process: a raw pointer needs N")
+            N = int(x.shape[0]) if len(x.shape) > 1 or self.V > 1 else int(np.prod(x.shape))
+        N = int(N)
+        if out is None:
+            out = DeviceBuffer((N, self.V), np.float64, zero=False)
+        if self._dcoef is None:
+            self._dcoef = DeviceBuffer.from_numpy(self.coef)
+        if self._dst is None:
+            self._dst = DeviceBuffer.from_numpy(self._st)
+        check(lib().mxg_scan_long_render(self.kind, self.V, N, _ptr(x), self._dcoef.ptr, self._dst.ptr, _ptr(out), self.stream), "mxg_scan_long_render")
+        self._keep = (x, out)   # (alive until the stream has run the launches)
+        return out
+
+    def host(self, x, advance=False):
+        """The host twin (mxg_scan_long_host, the device's bits) on numpy x [N][V] from the bank's state: (out, the state after it).
+        advance: the bank's state becomes that state."""
+        self._need_coef()
+        a = np.ascontiguousarray(x, np.float64).reshape(-1, self.V)
+        st, out = self.state(), np.empty_like(a)
+        check(lib().mxg_scan_long_host(self.kind, self.V, a.shape[0], a.ctypes.data, self.coef.ctypes.data, st.ctypes.data, out.ctypes.data), "mxg_scan_long_host")
+        if advance:
+            self.set_state(st)
+        return out, st
+
+    def sync(self):
+        check(lib().mxg_stream_sync(self.stream), "mxg_stream_sync")
