@@ -3,17 +3,8 @@
 // tests/test_sched_host.py fuzzes it against the step-by-step recurrences (tests/host_sched_fuzz.cpp).
 #pragma once
 #include <math.h>
-#include <string.h>
 
-#if defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#define MXG_HD_NOINLINE __device__
-#else
-#define MXG_HD static inline
-#define MXG_HD_NOINLINE static
-static inline long long __double_as_longlong(double x) { long long b; memcpy(&b, &x, 8); return b; }
-static inline double __longlong_as_double(long long b) { double x; memcpy(&x, &b, 8); return x; }
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -33,7 +24,7 @@ namespace {
 // as one ordinary floating-point step, so the sequence is the reference's, bit for bit.
 // Requires x >= 0, r > 0.  Advances at most kmax steps and stops right after the first step
 // whose result crosses the limit (x > limit, or x >= limit if `inclusive`); returns steps taken.
-MXG_HD int lowbit_exp(double v) {  // exponent of the lowest set bit of v (v > 0, normal)
+MXG_DEV int lowbit_exp(double v) {  // exponent of the lowest set bit of v (v > 0, normal)
     const long long b = __double_as_longlong(v);
     const int e = (int)((b >> 52) & 0x7ff);
     const unsigned long long m = ((unsigned long long)b & 0xFFFFFFFFFFFFFULL) | (1ULL << 52);
@@ -50,7 +41,7 @@ MXG_HD long long floor_div53(long long num, long long den) {
 }
 
 MXG_HD_NOINLINE int advance_until(double &x, const double r, const double limit, const bool inclusive, int kmax,
-                             bool &crossed) {
+                                  bool &crossed) {
     crossed = false;
     int done = 0;
     while (done < kmax) {
@@ -142,7 +133,7 @@ struct AddLine {
     int e;
     bool ok;
 };
-MXG_HD AddLine add_line(const double x, const double r, const double limit, const int n) {
+MXG_DEV AddLine add_line(const double x, const double r, const double limit, const int n) {
     AddLine l = {0, 0, 0, false};
     const long long xb = __double_as_longlong(x), rb = __double_as_longlong(r);
     const int e = (int)((xb >> 52) & 0x7ff), er = (int)((rb >> 52) & 0x7ff);
@@ -160,7 +151,7 @@ MXG_HD AddLine add_line(const double x, const double r, const double limit, cons
     l.ok = last < limit;
     return l;
 }
-MXG_HD double add_line_at(const AddLine &l, const int k) {
+MXG_DEV double add_line_at(const AddLine &l, const int k) {
     const long long Xk = l.X + (long long)k * l.c;
     return __longlong_as_double(((long long)l.e << 52) | (Xk & 0xFFFFFFFFFFFFFLL));
 }

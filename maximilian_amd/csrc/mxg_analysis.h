@@ -21,21 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef MXG_HD
-#if defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#else
-#define MXG_HD static inline
-#endif
-#endif
-
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 #define MXG_ANA_WANT_ZX 1
 #define MXG_ANA_WANT_ZCR 2
@@ -47,7 +33,7 @@ namespace mxg {
 namespace {
 
 // ---- maxiZeroCrossingDetector::zx ------------------------------------------------------------------------------------
-MXG_HOST_HD bool ana_zx(double &prev, double x) {
+MXG_HD bool ana_zx(double &prev, double x) {
     const bool res = prev <= 0 && x > 0;
     prev = x;
     return res;
@@ -65,16 +51,16 @@ struct AnaZcr {
     bool live;            // false: a shadow lane, computes and stores nothing
 };
 
-MXG_HOST_HD size_t ana_ring_words(size_t cap) { return (cap + 63) >> 6; }
+MXG_HD size_t ana_ring_words(size_t cap) { return (cap + 63) >> 6; }
 
-MXG_HOST_HD void ana_zcr_open(AnaZcr &z) {
+MXG_HD void ana_zcr_open(AnaZcr &z) {
     z.hw = z.idx >> 6;
     z.head = z.ring[(size_t)z.hw * z.stride];
     z.tw = -1;
     z.tail = 0;
 }
 
-MXG_HOST_HD double ana_zcr_step(AnaZcr &z, bool bit) {
+MXG_HD double ana_zcr_step(AnaZcr &z, bool bit) {
     const uint64_t m = (uint64_t)1 << (z.idx & 63);
     z.head = bit ? (z.head | m) : (z.head & ~m);
     int idx = z.idx + 1;
@@ -104,13 +90,13 @@ MXG_HOST_HD double ana_zcr_step(AnaZcr &z, bool bit) {
     return (double)z.count;
 }
 
-MXG_HOST_HD void ana_zcr_close(AnaZcr &z) {
+MXG_HD void ana_zcr_close(AnaZcr &z) {
     if (z.live) z.ring[(size_t)z.hw * z.stride] = z.head;
 }
 
 // ---- maxiEnvelopeFollowerType<T>::play -------------------------------------------------------------------------------
 template <typename T>
-MXG_HOST_HD T ana_follow(T &env, T attack, T release, T x) {
+MXG_HD T ana_follow(T &env, T attack, T release, T x) {
     const T a = (T)fabs(x);  // (the reference's fabs is the double one for both instantiations; |x| is exact either way)
     if (a > env) env = attack * (env - a) + a;
     else env = release * (env - a) + a;
@@ -119,11 +105,11 @@ MXG_HOST_HD T ana_follow(T &env, T attack, T release, T x) {
 
 // ---- maxiSampleAndHold::sah ------------------------------------------------------------------------------------------
 // (double)(size_t)t for t in [0, 2^64): trunc(t) is that value exactly; a negative or NaN time is 0 samples
-MXG_HOST_HD double ana_hold_samples(double ms, double sr) {
+MXG_HD double ana_hold_samples(double ms, double sr) {
     const double t = ms / 1000.0 * sr;
     return t >= 1.0 ? trunc(t) : 0.0;
 }
-MXG_HOST_HD double ana_sah(double &phase, double &value, double x, double hold) {
+MXG_HD double ana_sah(double &phase, double &value, double x, double hold) {
     if (phase >= hold) phase -= hold;
     if (phase < 1.0) value = x;
     phase++;

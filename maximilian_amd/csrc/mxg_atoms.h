@@ -20,11 +20,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define MXG_ATOMS_HD __host__ __device__ inline
-#else
-#define MXG_ATOMS_HD static inline
-#endif
+#include "mxg_hd.h"
+
 #if defined(__HIPCC__) || defined(__clang__)
 #define MXG_ATOMS_NO_CONTRACT _Pragma("clang fp contract(off)")
 #define MXG_ATOMS_NO_CONTRACT_ATTR
@@ -68,7 +65,7 @@ constexpr double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-
 }  // namespace atoms_detail
 constexpr float kAtomsMaxArg = 524288.0f;  // 2^19: the refusal bound on |maxPhase| + |startPhase|
 
-MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD double atoms_sin(double x) {
+MXG_ATOMS_NO_CONTRACT_ATTR MXG_HD double atoms_sin(double x) {
     MXG_ATOMS_NO_CONTRACT
     using namespace atoms_detail;
     const double fn = rint(x * kInvPio2);
@@ -89,7 +86,7 @@ MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD double atoms_sin(double x) {
         r = w + (((1.0 - w) - hz) + (z * p - y * t));
     } else {  // sin(y + t)
         const double v = z * y;
-        const double p = fma(z, fma(z, fma(z, fma(z, S6, S5), S4), S3), S2);
+        const double p = fma(z, fma(z, fma(z, fma(z, S6, S5), S4), atoms_detail::S3), S2);  // (S3 qualified: mxg_scan.h has a struct of that name)
         r = y - ((z * (0.5 * t - v * p) - t) - v * S1);
     }
     return (n & 2) ? -r : r;
@@ -100,7 +97,7 @@ struct GaborPar {
     float inc, maxPhase;
 };
 // A:58-60, :78.  `1.0 / length` and `maxPhase * TWOPI` are double operations rounded to float, the rest float.
-MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD GaborPar gabor_params(float freq, float sampleRate, unsigned length) {
+MXG_ATOMS_NO_CONTRACT_ATTR MXG_HD GaborPar gabor_params(float freq, float sampleRate, unsigned length) {
     MXG_ATOMS_NO_CONTRACT
     const float cycleLen = sampleRate / freq;
     float maxPhase = length / cycleLen;
@@ -110,18 +107,18 @@ MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD GaborPar gabor_params(float freq, float 
 }
 // What maxiAtomBookPlayer::play hands to createGabor for a book atom (A:211): linlin(frequency, 0, 1, 20, 20000) and amp / 40.0 are
 // doubles that the float parameters round; the sample rate is 44100 whatever maxiSettings says.
-MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD float book_freq(float frequency) {
+MXG_ATOMS_NO_CONTRACT_ATTR MXG_HD float book_freq(float frequency) {
     MXG_ATOMS_NO_CONTRACT
     double val = frequency;
     val = val < 1.0 ? val : 1.0;  // max(min(val, inMax), inMin), maximilian.h:803
     val = val < 0.0 ? 0.0 : val;
     return (float)(((val - 0.0) / (1.0 - 0.0) * (20000.0 - 20.0)) + 20.0);
 }
-MXG_ATOMS_HD float book_amp(float amp) { return (float)(amp / 40.0); }
+MXG_HD float book_amp(float amp) { return (float)(amp / 40.0); }
 constexpr float kBookSampleRate = 44100.0f;
 
 // atom[i]: env_f = (float)env[i]
-MXG_ATOMS_NO_CONTRACT_ATTR MXG_ATOMS_HD float gabor_sample(float env_f, float inc, float maxPhase, float startPhase, float amp, unsigned i) {
+MXG_ATOMS_NO_CONTRACT_ATTR MXG_HD float gabor_sample(float env_f, float inc, float maxPhase, float startPhase, float amp, unsigned i) {
     MXG_ATOMS_NO_CONTRACT
     const float x = inc * i;
     const float arg = (x * maxPhase) + startPhase;
@@ -156,13 +153,13 @@ struct AtomSeg {
 constexpr int kAtomSegWords = sizeof(AtomSeg) / 4;
 
 // A:108-110.  `int atomStart = startTime + pos` narrows to int as x86-64 does; the comparisons are in long.
-MXG_ATOMS_HD bool atom_due(int64_t startTime, uint32_t pos, int64_t sampleIdx, uint32_t n, int32_t &atomStart) {
+MXG_HD bool atom_due(int64_t startTime, uint32_t pos, int64_t sampleIdx, uint32_t n, int32_t &atomStart) {
     atomStart = (int32_t)(uint32_t)((uint64_t)startTime + pos);
     return (int64_t)atomStart >= sampleIdx && (int64_t)atomStart < sampleIdx + (int64_t)n;
 }
 // A:112-116 for a due entry: the samples it adds to this block and where.  BLOCK: from buffer[0] (the reference).  SAMPLE (extension):
 // from its own sample, atomStart - sampleIdx, and no further than the block.
-MXG_ATOMS_HD uint32_t atom_advance(uint32_t pos, uint32_t size, uint32_t n, int onset, int32_t atomStart, int64_t sampleIdx, uint32_t &dst_off) {
+MXG_HD uint32_t atom_advance(uint32_t pos, uint32_t size, uint32_t n, int onset, int32_t atomStart, int64_t sampleIdx, uint32_t &dst_off) {
     dst_off = onset == MXG_ATOM_ONSET_SAMPLE ? (uint32_t)((int64_t)atomStart - sampleIdx) : 0u;
     const int room = (int)(n - dst_off), left = (int)(size - pos);
     const int renderLength = room < left ? room : left;
@@ -172,13 +169,13 @@ MXG_ATOMS_HD uint32_t atom_advance(uint32_t pos, uint32_t size, uint32_t n, int 
 // ---- the book player ------------------------------------------------------------------------------------------------------------------
 // A:200-209: looped = idx % numSamples; atomIdx returns to 0 when looped < bufferSize; atoms are scheduled while
 // atom->position < (idx + bufferSize) % numSamples -- a float against a long, compared in float.
-MXG_ATOMS_HD int32_t player_looped(int64_t idx, uint32_t numSamples) { return (int32_t)(idx % (int64_t)numSamples); }
-MXG_ATOMS_HD float player_limit(int64_t idx, uint32_t n, uint32_t numSamples) { return (float)((idx + (int64_t)n) % (int64_t)numSamples); }
+MXG_HD int32_t player_looped(int64_t idx, uint32_t numSamples) { return (int32_t)(idx % (int64_t)numSamples); }
+MXG_HD float player_limit(int64_t idx, uint32_t n, uint32_t numSamples) { return (float)((idx + (int64_t)n) % (int64_t)numSamples); }
 // A:212 `addAtom(atomData, loopedSamplePos - atom->position)`: a float converted to unsigned.  Where that float is non-negative this is
 // the reference's value.  Where it is negative the reference's conversion is undefined (on x86-64 the atom lands 2^32 samples ahead
 // and never sounds); the evident intent is position - looped, the atom's distance into this block, and that is what this returns:
 // |looped - position|.
-MXG_ATOMS_HD uint32_t player_offset(int32_t looped, float position) {
+MXG_HD uint32_t player_offset(int32_t looped, float position) {
     float d = looped - position;
     if (d < 0.0f) d = -d;
     return (uint32_t)d;

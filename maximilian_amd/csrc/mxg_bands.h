@@ -24,13 +24,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 #define MXG_BARK_BANDS 24
 #define MXG_BARK_MAX_BUFFER 4096     /* the reference's barkScale[2048] */
@@ -84,15 +78,15 @@ inline int bnd_octave_map(float samplingRate, int nSpectrum, int perOctave, int 
 }
 
 // ---- maxiBark ----------------------------------------------------------------------------------------------------------------
-MXG_HOST_HD double bnd_bark_add(double sum, float x) { return sum + (double)x; }  // sum += normalisedSpectrum[j]  (:69)
+MXG_HD double bnd_bark_add(double sum, float x) { return sum + (double)x; }  // sum += normalisedSpectrum[j]  (:69)
 
-MXG_HOST_HD double bnd_bark_band(const float *row, int lo, int hi) {  // one band sum (:66-70)
+MXG_HD double bnd_bark_band(const float *row, int lo, int hi) {  // one band sum (:66-70)
     double sum = 0;
     for (int j = lo; j < hi; j++) sum = bnd_bark_add(sum, row[j]);
     return sum;
 }
 
-MXG_HOST_HD double bnd_bark_specific(double sum) {  // (:71)
+MXG_HD double bnd_bark_specific(double sum) {  // (:71)
 #if defined(__HIP_DEVICE_COMPILE__)
     // hipcc of ROCm 7.2 does not finish compiling pow() of a value it has traced back to an LDS load (a [64][25] tile read by its
     // lane and passed to pow(x, 0.23) is enough to reproduce it; exp(0.23 * log(x)) or sqrt(x) in its place compile at once).  The
@@ -103,7 +97,7 @@ MXG_HOST_HD double bnd_bark_specific(double sum) {  // (:71)
 }
 
 // v[24]: the band sums in, specificLoudness out; mx = relativeLoudness' max (:87-90), total = totalLoudness (:109-113)
-MXG_HOST_HD void bnd_bark_loudness(double *v, double &mx, double &total) {
+MXG_HD void bnd_bark_loudness(double *v, double &mx, double &total) {
     mx = 0;
     total = 0;
     for (int i = 0; i < MXG_BARK_BANDS; i++) {
@@ -114,7 +108,7 @@ MXG_HOST_HD void bnd_bark_loudness(double *v, double &mx, double &total) {
     }
 }
 
-MXG_HOST_HD void bnd_bark_relative(double *v, double mx) {  // (:92-94)
+MXG_HD void bnd_bark_relative(double *v, double mx) {  // (:92-94)
     for (int i = 0; i < MXG_BARK_BANDS; i++) v[i] = v[i] / mx;
 }
 
@@ -125,7 +119,7 @@ struct OctWalk {
 };
 
 // One bin of calculate() (L/maxiFFT.cpp:266-279).  True when a group closes: averages[from .. to) = avg.
-MXG_HOST_HD bool bnd_oct_bin(OctWalk &w, float x, int i, int avgidx, float intercept, float slope, float &avg, int &from, int &to) {
+MXG_HD bool bnd_oct_bin(OctWalk &w, float x, int i, int avgidx, float intercept, float slope, float &avg, int &from, int &to) {
     w.count++;
     const float eq = intercept + ((float)(i)*slope);
     w.sum = w.sum + (x * eq);
@@ -142,8 +136,8 @@ MXG_HOST_HD bool bnd_oct_bin(OctWalk &w, float x, int i, int avgidx, float inter
 }
 
 // One frame of calculate() without the peaks (:263-283).
-MXG_HOST_HD void bnd_octave_frame(const float *row, int nSpectrum, const int *spe2avg, int nAverages, float intercept, float slope,
-                                  float *averages) {
+MXG_HD void bnd_octave_frame(const float *row, int nSpectrum, const int *spe2avg, int nAverages, float intercept, float slope,
+                             float *averages) {
     OctWalk w = {0.0f, 0, 0};
     for (int i = 0; i < nSpectrum; i++) {
         float avg;
@@ -155,7 +149,7 @@ MXG_HOST_HD void bnd_octave_frame(const float *row, int nSpectrum, const int *sp
 }
 
 // One band of the peak update (:286-299).
-MXG_HOST_HD void bnd_peak_step(float avg, float &peak, int32_t &hold, int holdTime, float decay) {
+MXG_HD void bnd_peak_step(float avg, float &peak, int32_t &hold, int holdTime, float decay) {
     if (avg >= peak) {
         peak = avg;
         hold = holdTime;

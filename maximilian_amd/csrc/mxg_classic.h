@@ -29,13 +29,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 #define MXG_MAP_LINLIN 0
 #define MXG_MAP_LINEXP 1
@@ -57,7 +51,7 @@ struct ClsDyn {
     int attackphase, holdphase, releasephase;
 };
 
-MXG_HOST_HD double cls_gate(ClsDyn &s, double input, double threshold, int64_t holdtime, double attack, double release) {
+MXG_HD double cls_gate(ClsDyn &s, double input, double threshold, int64_t holdtime, double attack, double release) {
     if (fabs(input) > threshold && s.attackphase != 1) {
         s.holdcount = 0;
         s.releasephase = 0;
@@ -88,11 +82,11 @@ MXG_HOST_HD double cls_gate(ClsDyn &s, double input, double threshold, int64_t h
 }
 
 // 1 + log(ratio) with the caller's libm (host: the reference's own expression)
-MXG_HOST_HD double cls_makeup(double ratio) { return 1 + log(ratio); }
+MXG_HD double cls_makeup(double ratio) { return 1 + log(ratio); }
 // maxiDyn::setAttack / setRelease: pow(0.01, 1.0 / (ms * sampleRate * 0.001)) -- which compress() then uses as 1 + attack
-MXG_HOST_HD double cls_dyn_coeff(double ms, double sampleRate) { return pow(0.01, 1.0 / (ms * sampleRate * 0.001)); }
+MXG_HD double cls_dyn_coeff(double ms, double sampleRate) { return pow(0.01, 1.0 / (ms * sampleRate * 0.001)); }
 
-MXG_HOST_HD double cls_compress(ClsDyn &s, double input, double ratio, double makeup, double threshold, double attack, double release) {
+MXG_HD double cls_compress(ClsDyn &s, double input, double ratio, double makeup, double threshold, double attack, double release) {
     if (fabs(input) > threshold && s.attackphase != 1) {
         s.holdcount = 0;
         s.releasephase = 0;
@@ -126,13 +120,13 @@ struct ClsEnv {
 #define MXG_ENV_NONE INT64_MIN
 
 // an index into a table of n entries (n >= 1), held inside it
-MXG_HOST_HD int env_at(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+MXG_HD int env_at(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
 
 // count[v] is held inside [1, S] (a legal one is 2 .. S)
-MXG_HOST_HD int cls_env_count(int32_t count, size_t S) { return count < 1 ? 1 : (count > (int32_t)S ? (int32_t)S : count); }
+MXG_HD int cls_env_count(int32_t count, size_t S) { return count < 1 ? 1 : (count > (int32_t)S ? (int32_t)S : count); }
 
 // the increments of the two moving branches: they change with currentval, spp and startval
-MXG_HOST_HD void env_incs(ClsEnv &s) {
+MXG_HD void env_incs(ClsEnv &s) {
     s.up = ((s.currentval - s.startval) / s.spp);
     s.down = (((s.currentval - s.startval) * (-1)) / s.spp);
     s.incstart = s.startval;
@@ -143,7 +137,7 @@ MXG_HOST_HD void env_incs(ClsEnv &s) {
 // the advance is not reached), so nothing is read; an index that was loaded last time is not loaded again (the end-of-table
 // oscillation n -> n - 2 -> n comes back to the same entries on every second call), and the increments are formed again only
 // where startval moved.  Same inputs, same expressions: the reference's bits.
-MXG_HOST_HD void env_load(ClsEnv &s, const double *seg, size_t stride, int n, double sampleRate) {
+MXG_HD void env_load(ClsEnv &s, const double *seg, size_t stride, int n, double sampleRate) {
     if (s.valindex >= n) return;
     if (s.valindex != s.loaded) {
         const int i = env_at(s.valindex, n), j = i + 1 > n - 1 ? n - 1 : i + 1;
@@ -157,14 +151,14 @@ MXG_HOST_HD void env_load(ClsEnv &s, const double *seg, size_t stride, int n, do
     }
 }
 
-MXG_HOST_HD void cls_env_trigger(ClsEnv &s, int index, double amp, int n) {
+MXG_HD void cls_env_trigger(ClsEnv &s, int index, double amp, int n) {
     s.isPlaying = 1;
     s.valindex = index < 0 ? 0 : (index > n - 2 ? (n - 2 < 0 ? 0 : n - 2) : index);  // held inside [0, n - 2]
     s.amplitude = amp;
 }
 
 // one line() call; true: valindex changed, the caller runs env_load before the next call
-MXG_HOST_HD bool cls_env_line(ClsEnv &s, int n, double &out) {
+MXG_HD bool cls_env_line(ClsEnv &s, int n, double &out) {
     bool moved = false;
     if (s.isPlaying == 1) {
         if (s.currentval - s.amplitude > 0.0000001 && s.valindex < n) {
@@ -187,39 +181,39 @@ MXG_HOST_HD bool cls_env_line(ClsEnv &s, int n, double &out) {
 }
 
 // ---- maxiLagExp<double> ----------------------------------------------------------------------------------------------
-MXG_HOST_HD double cls_lag(double val, double alpha, double alphaReciprocal, double x) { return (alpha * x) + (alphaReciprocal * val); }
+MXG_HD double cls_lag(double val, double alpha, double alphaReciprocal, double x) { return (alpha * x) + (alphaReciprocal * val); }
 
 // ---- maxiMap / maxiConvert -------------------------------------------------------------------------------------------
 // std::max(std::min(val, inMax), inMin): min(a, b) = b < a ? b : a, max(a, b) = a < b ? b : a
-MXG_HOST_HD double cls_clip(double val, double inMin, double inMax) {
+MXG_HD double cls_clip(double val, double inMin, double inMax) {
     const double m = inMax < val ? inMax : val;
     return m < inMin ? inMin : m;
 }
-MXG_HOST_HD double cls_linlin(double val, double inMin, double inMax, double outMin, double outMax) {
+MXG_HD double cls_linlin(double val, double inMin, double inMax, double outMin, double outMax) {
     val = cls_clip(val, inMin, inMax);
     return ((val - inMin) / (inMax - inMin) * (outMax - outMin)) + outMin;
 }
-MXG_HOST_HD double cls_linexp(double val, double inMin, double inMax, double outMin, double outMax) {
+MXG_HD double cls_linexp(double val, double inMin, double inMax, double outMin, double outMax) {
     val = cls_clip(val, inMin, inMax);
     return pow((outMax / outMin), (val - inMin) / (inMax - inMin)) * outMin;
 }
 // log(inMax / inMin) of explin with the caller's libm
-MXG_HOST_HD double cls_explin_den(double inMin, double inMax) { return log(inMax / inMin); }
-MXG_HOST_HD double cls_explin(double val, double inMin, double inMax, double outMin, double outMax, double den) {
+MXG_HD double cls_explin_den(double inMin, double inMax) { return log(inMax / inMin); }
+MXG_HD double cls_explin(double val, double inMin, double inMax, double outMin, double outMax, double den) {
     val = cls_clip(val, inMin, inMax);
     return (log(val / inMin) / den * (outMax - outMin)) + outMin;
 }
-MXG_HOST_HD double cls_clamp(double v, double low, double high) {
+MXG_HD double cls_clamp(double v, double low, double high) {
     if (v > high) v = high;
     else if (v < low) v = low;
     return v;
 }
-MXG_HOST_HD double cls_amptodbs(double amp) { return log10(amp) * 20.0; }
-MXG_HOST_HD double cls_dbstoamp(double dbs) { return pow(10.0, dbs * 0.05); }
+MXG_HD double cls_amptodbs(double amp) { return log10(amp) * 20.0; }
+MXG_HD double cls_dbstoamp(double dbs) { return pow(10.0, dbs * 0.05); }
 
 // one element of `mode`; r0 .. r3 = inMin, inMax, outMin, outMax (clamp: low, high), aux = cls_explin_den (explin only)
 template <int MODE>
-MXG_HOST_HD double cls_map(double x, double r0, double r1, double r2, double r3, double aux) {
+MXG_HD double cls_map(double x, double r0, double r1, double r2, double r3, double aux) {
     if (MODE == MXG_MAP_LINLIN) return cls_linlin(x, r0, r1, r2, r3);
     if (MODE == MXG_MAP_LINEXP) return cls_linexp(x, r0, r1, r2, r3);
     if (MODE == MXG_MAP_EXPLIN) return cls_explin(x, r0, r1, r2, r3, aux);

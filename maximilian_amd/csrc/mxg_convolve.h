@@ -5,6 +5,7 @@
 #pragma once
 #include <vector>
 
+#include "mxg_hd.h"
 #include "mxg_spectral.h"
 
 namespace mxg {
@@ -85,19 +86,13 @@ struct conv_mac_args {
     float *SR, *SI;
 };
 
-#if defined(__HIPCC__)
-#define MXG_CONV_HD __host__ __device__ __forceinline__
-#else
-#define MXG_CONV_HD static inline
-#endif
-
-MXG_CONV_HD int conv_chunk(int R, int Kmax) { return R - (Kmax > 1 ? Kmax : 1) + 1; }  // frames per launch
-MXG_CONV_HD int conv_tiles(int c) { return (c + kConvM - 1) / kConvM; }
-MXG_CONV_HD conv_v2 conv_ld(const float *p) { return *reinterpret_cast<const conv_v2 *>(p); }
-MXG_CONV_HD void conv_st(float *p, const conv_v2 v) { *reinterpret_cast<conv_v2 *>(p) = v; }
+MXG_HD int conv_chunk(int R, int Kmax) { return R - (Kmax > 1 ? Kmax : 1) + 1; }  // frames per launch
+MXG_HD int conv_tiles(int c) { return (c + kConvM - 1) / kConvM; }
+MXG_HD conv_v2 conv_ld(const float *p) { return *reinterpret_cast<const conv_v2 *>(p); }
+MXG_HD void conv_st(float *p, const conv_v2 v) { *reinterpret_cast<conv_v2 *>(p) = v; }
 
 // lane `pair` (bins kConvBins * pair ...) of tile `tile` of stream v
-MXG_CONV_HD void conv_mac_lane(const conv_mac_args &g, size_t v, int tile, int pair) {
+MXG_HD void conv_mac_lane(const conv_mac_args &g, size_t v, int tile, int pair) {
     constexpr int M = kConvM;
     const int bins = g.bins, i0 = pair * kConvBins;
     const int K = g.K[v], m0 = tile * M;

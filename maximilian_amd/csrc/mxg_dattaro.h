@@ -27,13 +27,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_DT_HD
-#if defined(__HIPCC__)
-#define MXG_DT_HD __host__ __device__ __forceinline__
-#else
-#define MXG_DT_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -46,20 +40,20 @@ constexpr int DT_AP0 = 0, DT_AP1 = 1, DT_AP4 = 2, DT_AP5 = 3, DT_AP6 = 4, DT_AP7
 constexpr int DT_LP0 = 0, DT_LP1 = 1, DT_LP2 = 2, DT_SIGL = 3, DT_SIGR = 4;
 
 // lengths at 29.8 kHz (fbap[0], [1], [4..7]; dattarofixdellengths[0..3]) and the tap positions there
-MXG_DT_HD constexpr int dt_orig_len(int r) {
+MXG_HD constexpr int dt_orig_len(int r) {
     return r == 0 ? 142 : r == 1 ? 107 : r == 2 ? 908 : r == 3 ? 2656 : r == 4 ? 672 : r == 5 ? 1800 : r == 6 ? 4217
            : r == 7 ? 3163 : r == 8 ? 4453 : 3720;
 }
-MXG_DT_HD constexpr int dt_orig_tap(int j) {
+MXG_HD constexpr int dt_orig_tap(int j) {
     return j == 0 ? 266 : j == 1 ? 2974 : j == 2 ? 1913 : j == 3 ? 1996 : j == 4 ? 1990 : j == 5 ? 187 : j == 6 ? 1066
            : j == 7 ? 353 : j == 8 ? 3627 : j == 9 ? 1228 : j == 10 ? 2673 : j == 11 ? 2111 : j == 12 ? 335 : 121;
 }
 // the ring tap j reads
-MXG_DT_HD constexpr int dt_tap_ring(int j) {
+MXG_HD constexpr int dt_tap_ring(int j) {
     return (j == 0 || j == 1 || j == 11) ? DT_D0 : (j == 2 || j == 12) ? DT_AP5 : (j == 3 || j == 13) ? DT_D1
            : (j == 4 || j == 7 || j == 8) ? DT_D2 : (j == 5 || j == 9) ? DT_AP7 : DT_D3;
 }
-MXG_DT_HD constexpr int dt_steps(int r) { return r < 2 ? 2 : 1; }  // steps per sample
+MXG_HD constexpr int dt_steps(int r) { return r < 2 ? 2 : 1; }  // steps per sample
 
 // the constructor's float arithmetic: floor(((float)orig / 29.8f) * ((float)sampleRate / 1000.0f))
 static inline int dt_scale(int orig, uint32_t sample_rate) {
@@ -92,9 +86,9 @@ static inline DtLayout dt_layout(uint32_t sample_rate) {
 // steps*L <= D.  A tap at position p reads what was written D-1-p samples earlier: the sample's own write (distance 0),
 // or, when the distance is at least L, something older than the tile -- provided every tap read of the tile comes before
 // any of its writes, because the slot may be overwritten later in the same tile.
-MXG_DT_HD constexpr bool dt_tile_ok_ring(int D, int steps, int T) { return steps * T <= D; }
-MXG_DT_HD constexpr int dt_tap_dist(int D, int p) { return D - 1 - p; }
-MXG_DT_HD constexpr bool dt_tile_ok_tap(int D, int p, int T) { return dt_tap_dist(D, p) == 0 || dt_tap_dist(D, p) >= T; }
+MXG_HD constexpr bool dt_tile_ok_ring(int D, int steps, int T) { return steps * T <= D; }
+MXG_HD constexpr int dt_tap_dist(int D, int p) { return D - 1 - p; }
+MXG_HD constexpr bool dt_tile_ok_tap(int D, int p, int T) { return dt_tap_dist(D, p) == 0 || dt_tap_dist(D, p) >= T; }
 // A sample rate is accepted iff every length lies in [2, DT_MAX_LEN] and a tile of T samples is legal on the eight tank
 // rings and on all fourteen taps.  (The two input rings are walked in sub-tiles where they are shorter than 2*T.)
 static inline bool dt_accepts(const DtLayout &L, int T) {
@@ -107,38 +101,38 @@ static inline bool dt_accepts(const DtLayout &L, int T) {
     return true;
 }
 // samples per parallel pass over the two doubly stepped input rings
-MXG_DT_HD int dt_in_sub_len(int D0, int D1, int T) {
+MXG_HD int dt_in_sub_len(int D0, int D1, int T) {
     const int D = D0 < D1 ? D0 : D1;
     return D / 2 < T ? D / 2 : T;
 }
 
 // ---- the per-sample arithmetic -----------------------------------------------------------------------------------
-MXG_DT_HD double dt_lopass(double y, double c, double x) { return y + c * (x - y); }
+MXG_HD double dt_lopass(double y, double c, double x) { return y + c * (x - y); }
 // one allpass step: `t` comes in as the stage's input and leaves as its output; returns what the ring slot gets
-MXG_DT_HD double dt_allpass(double d, double &t, double fb) {
+MXG_HD double dt_allpass(double d, double &t, double fb) {
     const double s = t + d * fb;
     t = d + (s * (-fb));
     return s;
 }
-MXG_DT_HD double dt_cross(double d, double sig) { return d + 0.3 * sig; }
-MXG_DT_HD double dt_mix(double a, double b, double c, double d, double e, double f, double g) { return a + b - c + d - e - f - g; }
+MXG_HD double dt_cross(double d, double sig) { return d + 0.3 * sig; }
+MXG_HD double dt_mix(double a, double b, double c, double d, double e, double f, double g) { return a + b - c + d - e - f - g; }
 
 // ---- slot arithmetic ---------------------------------------------------------------------------------------------
 // A stored index outside its ring restarts at slot 0 (the reference cannot produce one).
-MXG_DT_HD int dt_idx_fix(int32_t idx, int D) { return (uint32_t)idx < (uint32_t)D ? idx : 0; }
+MXG_HD int dt_idx_fix(int32_t idx, int D) { return (uint32_t)idx < (uint32_t)D ? idx : 0; }
 // the slot of the k-th step after `idx`, 0 <= k <= D
-MXG_DT_HD int dt_slot(int idx, int k, int D) {
+MXG_HD int dt_slot(int idx, int k, int D) {
     const int s = idx + k;
     return s >= D ? s - D : s;
 }
 // the slot gettap(p) reads after the k-th step after `idx` has been taken (k steps done, index at idx + k + 1), 0 <= k < D
-MXG_DT_HD int dt_tap_slot(int idx, int k, int p, int D) {
+MXG_HD int dt_tap_slot(int idx, int k, int p, int D) {
     int s = idx + k + 1 + p;
     if (s >= D) s -= D;
     if (s >= D) s -= D;
     return s;
 }
-MXG_DT_HD int dt_idx_after(int idx, int k, int D) { return (idx + k) % D; }
+MXG_HD int dt_idx_after(int idx, int k, int D) { return (idx + k) % D; }
 
 // ---- one voice, one sample at a time, over the bank's state layout ---------------------------------------------------
 // rings [V][S] (voice-major, ring r at L.off[r]), idx int32 [V][10], state [V][5] = lp0 lp1 lp2 sigl sigr.

@@ -24,17 +24,13 @@
 // playHead++; } -- ticker never writes lastCount, so with lastCount = 0 a tick is the one sample per wrap on which the phasor
 // returns a phase >= 1.
 #pragma once
-#if defined(__HIPCC__) && !defined(MXG_STEP_HOST_CALLABLE)
-// mxg_drum_host / mxg_clock_host run these step functions on the host pass: the translation unit is compiled with
-// -DMXG_STEP_HOST_CALLABLE (csrc/Makefile), which mxg_env.h, mxg_osc.h, mxg_fx.h and mxg_seq.h read, whatever the include order
-#error "a translation unit that includes mxg_drums.h is compiled with -DMXG_STEP_HOST_CALLABLE"
-#endif
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
 
+#include "mxg_hd.h"
 #include "mxg_osc.h"
 #include "mxg_env.h"
 #include "mxg_fx.h"
@@ -73,14 +69,14 @@ struct DrumState {
 };
 
 template <int KIND>
-MXG_HOST_HD void drum_par_init(DrumPar &p) {
+MXG_HD void drum_par_init(DrumPar &p) {
     if constexpr (KIND == MXG_DRUM_HATS) p.q = osc_pre<MXG_OSC_SINEBUF>(p.pitch, p.sr, 0.0, 0.0);
 }
 
 // One play().  tab: the kick's sin / cos table (MXG_SINTAB, mxg_sincos.h), the hats' sineBuffer with its guard entry (maxi_tables.h);
 // unused by the snare.  rnd: this call's rand() draw (snare, hats).
 template <int KIND>
-MXG_HOST_HD double drum_step(DrumState &s, const DrumPar &p, bool trig, int32_t rnd, const double *tab, const SinTabK k) {
+MXG_HD double drum_step(DrumState &s, const DrumPar &p, bool trig, int32_t rnd, const double *tab, const SinTabK k) {
     double envOut = env_adsr(s.env, 1., trig ? 1 : 0);
     if (p.flags & MXG_DRUM_INVERSE) envOut = fabs(1 - envOut);
     double output, hold;
@@ -112,7 +108,7 @@ MXG_HOST_HD double drum_step(DrumState &s, const DrumPar &p, bool trig, int32_t 
 
 // One ticker().  q: osc_pre<MXG_OSC_PHASOR>(bps); returns tick, writes currentCount.  The conversion of floor()'s double to the
 // int member is x86-64's (fx_cvt_i32).
-MXG_HOST_HD bool clock_tick(double &clk, const OscPre &q, int32_t lastCount, int32_t &currentCount, long long &playHead) {
+MXG_HD bool clock_tick(double &clk, const OscPre &q, int32_t lastCount, int32_t &currentCount, long long &playHead) {
     currentCount = fx_cvt_i32(floor(seq_clock_tick(clk, q)));
     const bool tick = lastCount != currentCount;
     playHead += tick ? 1 : 0;
@@ -136,7 +132,7 @@ struct DrumArgs {
 
 // the parameters and the state of voice v (arrays on the device or on the host)
 template <int KIND>
-MXG_HOST_HD void drum_load(const DrumArgs &A, size_t v, DrumPar &p, DrumState &s) {
+MXG_HD void drum_load(const DrumArgs &A, size_t v, DrumPar &p, DrumState &s) {
     const size_t V = A.V;
     p.pitch = A.pitch[v];
     p.shape = A.shape ? A.shape[v] : 0.0;
@@ -153,7 +149,7 @@ MXG_HOST_HD void drum_load(const DrumArgs &A, size_t v, DrumPar &p, DrumState &s
     s.f1 = A.fst[V + v];
     s.f2 = A.fst[2 * V + v];
 }
-MXG_HOST_HD void drum_store(const DrumArgs &A, size_t v, const DrumState &s) {
+MXG_HD void drum_store(const DrumArgs &A, size_t v, const DrumState &s) {
     const size_t V = A.V;
     A.phase[v] = s.phase;
     env_store(s.env, V, v, A.dst, A.ist);

@@ -17,20 +17,7 @@
 #include <stdint.h>
 
 #include "mxg_envgen.h"
-
-#ifndef MXG_HD
-#if defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#else
-#define MXG_HD static inline
-#endif
-#endif
-
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
+#include "mxg_hd.h"
 
 #define MXG_DYN_PEAK 0
 #define MXG_DYN_RMS 1
@@ -258,7 +245,7 @@ MXG_HD void rms_voice_block(const RmsArgs &A, size_t v) {
 
 // maxiEnvGen::setTime(index, ms) (H:2449-2462 with setupSegmentTime H:2532-2546, accumulatedTime = 0) on one row of the
 // [S][6] table (startlevel, endlevel, gradient, curve, length, hold).  Returns the reference's `error`.
-MXG_HOST_HD int dyn_envgen_set_time(double *tab, size_t S, size_t index, double ms, double sr) {
+MXG_HD int dyn_envgen_set_time(double *tab, size_t S, size_t index, double ms, double sr) {
     const double HOLD = -46692.0;
     if (index >= S) return 1;  // (index == S passes the reference's test and writes past its vector: refused here)
     bool contains_hold = false;

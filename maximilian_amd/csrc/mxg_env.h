@@ -7,16 +7,8 @@
 #else  // host build of the same text (tests/host_env.cpp: state machine and steady-state paths against the oracle)
 #include <stddef.h>
 #include <stdint.h>
-#include <string.h>
-#define __device__
-#define __forceinline__ inline
 #endif
-// MXG_STEP_HOST_CALLABLE (a -D of the translation unit, csrc/Makefile: drums.hip): these functions also run on its host pass
-#if defined(__HIPCC__) && defined(MXG_STEP_HOST_CALLABLE)
-#define MXG_ENV_HD __host__ __device__ __forceinline__
-#else
-#define MXG_ENV_HD __device__ __forceinline__
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -28,9 +20,9 @@ struct Env {
     int attackphase, decayphase, sustainphase, holdphase, releasephase;
 };
 
-MXG_ENV_HD void env_load(Env &e, size_t V, size_t v, const double *par,
-                                         const int64_t *holdtime, const double *dst,
-                                         const int64_t *ist) {
+MXG_HD void env_load(Env &e, size_t V, size_t v, const double *par,
+                     const int64_t *holdtime, const double *dst,
+                     const int64_t *ist) {
     e.attack = par[v];
     e.decay = par[V + v];
     e.sustain = par[2 * V + v];
@@ -45,8 +37,8 @@ MXG_ENV_HD void env_load(Env &e, size_t V, size_t v, const double *par,
     e.holdphase = (int)ist[4 * V + v];
     e.releasephase = (int)ist[5 * V + v];
 }
-MXG_ENV_HD void env_store(const Env &e, size_t V, size_t v, double *dst,
-                                          int64_t *ist) {
+MXG_HD void env_store(const Env &e, size_t V, size_t v, double *dst,
+                      int64_t *ist) {
     dst[v] = e.amplitude;
     dst[V + v] = e.output;
     ist[v] = e.holdcount;
@@ -66,7 +58,7 @@ MXG_ENV_HD void env_store(const Env &e, size_t V, size_t v, double *dst,
 // output = input * g with g the amplitude at the LAST such statement that fired, or leaves output alone (upd = false) -- a select among
 // products of one input is the product with the selected factor, the same bits.  The state machine is this function; env_adsr
 // multiplies once.  The fused voice's two-stage form (voice.hip, voice_split_kernel) runs the gains a stage ahead of the filter.
-MXG_ENV_HD double env_adsr_gain(Env &e, int trigger, bool &upd) {
+MXG_HD double env_adsr_gain(Env &e, int trigger, bool &upd) {
     const bool t1 = trigger == 1;
     // C:1417-1423
     const bool c1 = t1 && e.attackphase != 1 && e.holdphase != 1 && e.decayphase != 1;
@@ -114,7 +106,7 @@ MXG_ENV_HD double env_adsr_gain(Env &e, int trigger, bool &upd) {
     upd = a || d || h || s || r;
     return g;
 }
-MXG_ENV_HD double env_adsr(Env &e, double input, int trigger) {
+MXG_HD double env_adsr(Env &e, double input, int trigger) {
     bool upd;
     const double g = env_adsr_gain(e, trigger, upd);
     e.output = upd ? input * g : e.output;
@@ -127,21 +119,21 @@ MXG_ENV_HD double env_adsr(Env &e, double input, int trigger) {
 // while it is > 0).  A wavefront whose lanes are all in one of them, with the (shared, scalar) gate
 // constant over a chunk, runs the chunk without the predicated state machine -- same operations on
 // the same values, so bit-identical, at ~1/6 of the VALU work.
-MXG_ENV_HD bool env_in_sustain(const Env &e) {
+MXG_HD bool env_in_sustain(const Env &e) {
     return e.attackphase != 1 && e.decayphase != 1 && e.releasephase != 1 && e.holdphase == 1 &&
            e.holdcount >= e.holdtime;
 }
-MXG_ENV_HD bool env_in_release(const Env &e) {
+MXG_HD bool env_in_release(const Env &e) {
     // holdphase == 0, not merely != 1: C:1456 stores 0 into it on every such sample, so any other value (a state
     // uploaded by the host) has to go through the state machine once
     return e.attackphase != 1 && e.decayphase != 1 && e.releasephase == 1 && e.holdphase == 0 &&
            e.holdcount >= e.holdtime;
 }
-MXG_ENV_HD double env_sustain_tick(Env &e, double input) {  // gate == 1
+MXG_HD double env_sustain_tick(Env &e, double input) {  // gate == 1
     e.output = input * e.amplitude;  // C:1452
     return e.output;
 }
-MXG_ENV_HD double env_release_tick(Env &e, double input) {  // gate != 1
+MXG_HD double env_release_tick(Env &e, double input) {  // gate != 1
     const bool r = e.amplitude > 0.;  // C:1460
     const double ampR = e.amplitude * e.release;
     e.amplitude = r ? ampR : e.amplitude;
@@ -166,17 +158,13 @@ MXG_ENV_HD double env_release_tick(Env &e, double input) {  // gate != 1
 // instead of ~100.
 // (gain form, as env_adsr_gain: g[i] = the amplitude sample i multiplies its input by, upd = false for an idle lane, whose output stays)
 template <int U>
-MXG_ENV_HD bool env_steady_gains(Env &e, const bool gate, double (&g)[U], bool &upd) {
+MXG_DEV bool env_steady_gains(Env &e, const bool gate, double (&g)[U], bool &upd) {
     const bool ap = e.attackphase == 1, dp = e.decayphase == 1, hp = e.holdphase == 1, rp = e.releasephase == 1;
     const bool ge = e.holdcount >= e.holdtime;
     long long hb;
     {
         double t = e.amplitude;
-#if defined(__HIPCC__)
         hb = __double_as_longlong(t);
-#else
-        memcpy(&hb, &t, 8);
-#endif
     }
     const bool nonneg = hb >= 0;  // sign bit clear: +0 and positive values (and positive NaNs, which fail every test below)
     // stage of this lane (exactly one phase flag set, the others exactly as the stage leaves them)
@@ -207,7 +195,7 @@ MXG_ENV_HD bool env_steady_gains(Env &e, const bool gate, double (&g)[U], bool &
     return ok;
 }
 template <int U>
-MXG_ENV_HD bool env_steady_chunk(Env &e, const double (&x)[U], const bool gate, double (&o)[U]) {
+MXG_DEV bool env_steady_chunk(Env &e, const double (&x)[U], const bool gate, double (&o)[U]) {
     double g[U];
     bool upd;
     const bool ok = env_steady_gains<U>(e, gate, g, upd);
@@ -224,7 +212,7 @@ MXG_ENV_HD bool env_steady_chunk(Env &e, const double (&x)[U], const bool gate, 
 // gate state of a full chunk from its (already fetched, wave-uniform) trigger values:
 // +1 all == 1, -1 all != 1, 0 mixed.  Scalar work.
 template <int U>
-MXG_ENV_HD int gate_of_chunk(const int (&t)[U]) {
+MXG_HD int gate_of_chunk(const int (&t)[U]) {
     int on = 0;
 #pragma unroll
     for (int i = 0; i < U; i++) on += (t[i] == 1) ? 1 : 0;
@@ -232,7 +220,7 @@ MXG_ENV_HD int gate_of_chunk(const int (&t)[U]) {
 }
 
 // C:1319-1358
-MXG_ENV_HD double env_ar(Env &e, double input, int trigger) {
+MXG_HD double env_ar(Env &e, double input, int trigger) {
     const double attack = e.attack, release = e.release;
     const long long holdtime = e.holdtime;
     if (trigger == 1 && e.attackphase != 1 && e.holdphase != 1) {

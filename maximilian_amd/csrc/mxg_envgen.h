@@ -9,9 +9,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-#define __device__
-#define __forceinline__ inline
 #endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -29,7 +28,7 @@ struct EgState {
     bool nxc;                     // nxcHappened
 };
 
-__device__ __forceinline__ bool on_zx(double &prev, bool &first, double input) {  // H:569-579
+MXG_DEV bool on_zx(double &prev, bool &first, double input) {  // H:569-579
     const bool zx = (prev <= 0.0 || first) && input > 0;
     prev = input;
     first = false;
@@ -37,8 +36,8 @@ __device__ __forceinline__ bool on_zx(double &prev, bool &first, double input) {
 }
 
 // tab: [S][6] = startlevel, endlevel, gradient, curve, length, hold (mxg_envgen_stages_host).  Returns envval.
-__device__ __forceinline__ double envgen_tick(EgState &e, const double *tab, long long S, bool loop, bool retrigger,
-                                              double trigger) {
+MXG_DEV double envgen_tick(EgState &e, const double *tab, long long S, bool loop, bool retrigger,
+                           double trigger) {
     int entry = e.state;  // the switch's fall-through, made explicit
     if (entry == EG_WAITING) {  // H:2279-2292
         if (on_zx(e.tprev, e.tfirst, trigger)) {
@@ -118,7 +117,7 @@ struct EgRow {
     bool valid;         // phase inside the table (phase == S -- reachable through an uploaded state -- is play()'s end-of-envelope
                         // test, H:2349-2355, which runs on every sample in every state: never a steady chunk)
 };
-__device__ __forceinline__ EgRow envgen_row(const double *tab, long long S, long long phase) {
+MXG_DEV EgRow envgen_row(const double *tab, long long S, long long phase) {
     EgRow r = {0.0, 0.0, 0.0, 0, false, false};
     if (phase < 0 || phase >= S) return r;
     r.valid = true;
@@ -135,7 +134,7 @@ struct EgCross {
     bool pos, neg;       // a crossing between two samples of the chunk: of the trigger (trigDetector / retriggerDetector), of -trigger (holdDetector)
 };
 template <int U>
-__device__ __forceinline__ EgCross envgen_cross(const double (&t)[U]) {
+MXG_DEV EgCross envgen_cross(const double (&t)[U]) {
     EgCross c = {t[0], t[U - 1], false, false};
 #pragma unroll
     for (int i = 1; i < U; i++) {
@@ -145,7 +144,7 @@ __device__ __forceinline__ EgCross envgen_cross(const double (&t)[U]) {
     return c;
 }
 template <int U>
-__device__ __forceinline__ bool envgen_steady_chunk(EgState &e, const EgRow &r, bool retrigger, const EgCross &x, double (&o)[U]) {
+MXG_DEV bool envgen_steady_chunk(EgState &e, const EgRow &r, bool retrigger, const EgCross &x, double (&o)[U]) {
     // linlin's clamp (H:801-805) is the identity on [0, 1]; currentlevel only grows (gradient >= 0), so the first and the last
     // level used bound the chunk.  (U - 1) additions in the reference's order:
     double cl[U + 1];
@@ -180,13 +179,13 @@ __device__ __forceinline__ bool envgen_steady_chunk(EgState &e, const EgRow &r, 
 }
 
 // the [5][V] / [7][V] state arrays of mxg_envgen_render
-__device__ __forceinline__ void envgen_load(EgState &e, size_t V, size_t v, const double *dst, const int64_t *ist) {
+MXG_DEV void envgen_load(EgState &e, size_t V, size_t v, const double *dst, const int64_t *ist) {
     e.envval = dst[v]; e.currentlevel = dst[V + v];
     e.tprev = dst[2 * V + v]; e.hprev = dst[3 * V + v]; e.rprev = dst[4 * V + v];
     e.phase = ist[v]; e.state = (int)ist[V + v]; e.nxc = ist[2 * V + v] != 0; e.counter = ist[3 * V + v];
     e.tfirst = ist[4 * V + v] != 0; e.hfirst = ist[5 * V + v] != 0; e.rfirst = ist[6 * V + v] != 0;
 }
-__device__ __forceinline__ void envgen_store(const EgState &e, long long S, size_t V, size_t v, double *dst, int64_t *ist) {
+MXG_DEV void envgen_store(const EgState &e, long long S, size_t V, size_t v, double *dst, int64_t *ist) {
     const bool in = e.phase < S;
     dst[v] = e.envval;
     dst[V + v] = in ? e.currentlevel : 0.0;

@@ -12,15 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef MXG_HD
-#if defined(__HIPCC__) && defined(MXG_STEP_HOST_CALLABLE)  // (csrc/Makefile: drums.hip runs these functions on its host pass too)
-#define MXG_HD __host__ __device__ __forceinline__
-#elif defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#else
-#define MXG_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {

@@ -13,6 +13,7 @@
 // A per-sample value is what a patch passes to play() in that sample: speed / rate move `position` at every sample, a grain takes
 // the values of the sample it is born in.
 #pragma once
+#include "mxg_hd.h"
 #include "mxg_sched.h"
 
 #ifndef MXG_GPOOL_PS_A
@@ -50,7 +51,7 @@ constexpr int kGpTooMany = 1, kGpRndExhausted = 2, kGpForeign = 4, kGpStep = 5;
 struct GpLoop {
     double loopStart, loopEnd, loopLength;
 };
-__device__ __forceinline__ GpLoop gp_loop(uint64_t loopStart, uint64_t loopEnd) {
+MXG_DEV GpLoop gp_loop(uint64_t loopStart, uint64_t loopEnd) {
     GpLoop l;
     l.loopStart = (double)loopStart;
     l.loopEnd = (double)loopEnd;
@@ -61,8 +62,8 @@ __device__ __forceinline__ GpLoop gp_loop(uint64_t loopStart, uint64_t loopEnd) 
 // One sample of the scheduler.  c holds this sample's speed / rate / pm; bpos is mode 4's position argument.
 // Modes 0, 2 and 3 are sched_step itself.
 template <int MODE>
-__device__ __forceinline__ bool gp_sched_step(SchedState &q, const SchedConst &c, const GpLoop &lp, const double bpos, size_t n,
-                                              double &pos0, double &inc, int &failed) {
+MXG_DEV bool gp_sched_step(SchedState &q, const SchedConst &c, const GpLoop &lp, const double bpos, size_t n,
+                           double &pos0, double &inc, int &failed) {
     if constexpr (MODE == 1) {  // maxiStretch::play :514-526
         q.position = q.position + c.rate;
         q.looper += 1.0;
@@ -88,15 +89,15 @@ __device__ __forceinline__ bool gp_sched_step(SchedState &q, const SchedConst &c
 }
 
 // a live grain handed in through gst must be one this plan could have made in THIS stream's slot (grains.hip carried_grain_ok)
-__device__ __forceinline__ bool gp_carried_ok(double pos, double inc, double idx, double dur, double dlen, int sampleDur) {
+MXG_DEV bool gp_carried_ok(double pos, double inc, double idx, double dur, double dlen, int sampleDur) {
     return dur == (double)sampleDur && idx >= 0.0 && idx < dur && pos >= 0.0 && pos <= dlen && fabs(inc) <= dlen;
 }
 
 // maxiGrain::play :216-245 without the window: moves pos, returns the interpolated sample.  pos stays inside [0, len]; the one
 // value outside [0, len) -- pos + len rounding up to len exactly after a wrap from below zero -- reads the zero an uploaded
 // sample and a pool slot keep behind their last element (the oracle's guard element), without touching memory.
-__device__ __forceinline__ double gp_grain_read(double &gpos, const double ginc, const double dlen, const size_t len,
-                                                const double *buf) {
+MXG_DEV double gp_grain_read(double &gpos, const double ginc, const double dlen, const size_t len,
+                             const double *buf) {
     double pos = gpos + ginc;
     if (pos >= dlen)
         pos -= dlen;
@@ -122,7 +123,7 @@ struct GpStream {
     SchedConst sc;
     bool psA, psB, psP;
     // false: a slot index outside the pool or an empty slot
-    __device__ __forceinline__ bool setup(const GpArgs &A, const size_t s) {
+    MXG_DEV bool setup(const GpArgs &A, const size_t s) {
         const size_t S = A.S;
         const size_t r = A.slot ? (size_t)A.slot[s] : s;
         uint64_t l64 = r < A.R ? A.len[r] : 0;
@@ -157,7 +158,7 @@ struct GpStream {
         return true;
     }
     // the arguments play() is handed in sample n
-    __device__ __forceinline__ void sample(const GpArgs &A, const size_t s, const size_t n) {
+    MXG_DEV void sample(const GpArgs &A, const size_t s, const size_t n) {
         if (psA) {
             av = A.a[n * A.S + s];
             sc.speed = av;
@@ -174,7 +175,7 @@ struct GpStream {
 // The whole of stream s for A.T samples: K27's walk.  win = the window table (the kernel stages it in LDS).  Returns the
 // stream's failure code (0 = none).
 template <int MODE>
-__device__ __forceinline__ int gp_walk_stream(const GpArgs &A, const size_t s, const double *win) {
+MXG_DEV int gp_walk_stream(const GpArgs &A, const size_t s, const double *win) {
     const size_t S = A.S;
     int failed = 0;
     double *op = A.out + s;
@@ -313,7 +314,7 @@ constexpr int kGpListOverflow = 3;
 // multiple of u = 2^(e-52); r = (R + f) u, and round-to-nearest (symmetric in sign) takes off R ulps (f < 1/2) or R + 1 (f > 1/2)
 // on every step: X_k = X - k c.  The jump stops one ulp short of 2^e -- at 2^e itself the exact difference lies on the finer grid
 // below -- and the tie f == 1/2, the step across the binade's lower edge, zero, subnormals and the crossing step are plain steps.
-__device__ __forceinline__ int gp_retreat_until(double &x, const double r, const int kmax, bool &crossed) {
+MXG_DEV int gp_retreat_until(double &x, const double r, const int kmax, bool &crossed) {
     crossed = false;
     int done = 0;
     while (done < kmax) {
@@ -359,7 +360,7 @@ __device__ __forceinline__ int gp_retreat_until(double &x, const double r, const
 // pos after `steps` calls of maxiGrain::play's `pos += inc` with its wrap (:224-228), from a pos inside [0, dlen]: between two wraps
 // the exact multi-step forms (advance_until upwards, gp_retreat_until downwards), the wrap itself and whatever they exclude as the
 // plain step.  The same additions in the same order as the walk's, whatever the sign of the step.
-__device__ __forceinline__ double gp_advance(double pos, const double inc, const double dlen, int steps) {
+MXG_DEV double gp_advance(double pos, const double inc, const double dlen, int steps) {
     if (inc > 0.0 && pos >= 0.0) {
         while (steps > 0) {
             bool wrapped;
@@ -398,7 +399,7 @@ __device__ __forceinline__ double gp_advance(double pos, const double inc, const
 }
 
 template <int MODE>
-__device__ __forceinline__ int gp_tile_sched(const GpArgs &A, const GpLists &L, const size_t s) {
+MXG_DEV int gp_tile_sched(const GpArgs &A, const GpLists &L, const size_t s) {
     const size_t S = A.S;
     const int T = (int)A.T, dur = A.sampleDur;
     int failed = 0;
@@ -490,8 +491,8 @@ __device__ __forceinline__ int gp_tile_sched(const GpArgs &A, const GpLists &L, 
 
 // one grain's share of sample n0 + j: the grain has taken k0 steps from x when the tile starts (its first step inside the tile is
 // lane j0's, at age m0).  Everything but j is the same for the 64 lanes of a tile.
-__device__ __forceinline__ void gp_tile_grain(double &total, double x, const double inc, const int k0, const int j0, const int m0, const int j,
-                                              const int dur, const double dlen, const size_t len, const double *buf, const double *win) {
+MXG_DEV void gp_tile_grain(double &total, double x, const double inc, const int k0, const int j0, const int m0, const int j,
+                           const int dur, const double dlen, const size_t len, const double *buf, const double *win) {
     const double x0 = gp_advance(x, inc, dlen, k0);
     const AddLine line = add_line(x0, inc, dlen, kGpTile);
     const int m = m0 + (j - j0);
@@ -516,8 +517,8 @@ __device__ __forceinline__ void gp_tile_grain(double &total, double x, const dou
 }
 
 // out[n0 + j][s], n0 a multiple of 64
-__device__ __forceinline__ double gp_tile_sample(const GpArgs &A, const GpLists &L, const size_t s, const int n0, const int j,
-                                                 const double *win) {
+MXG_DEV double gp_tile_sample(const GpArgs &A, const GpLists &L, const size_t s, const int n0, const int j,
+                              const double *win) {
     const size_t S = A.S;
     const int dur = A.sampleDur;
     const size_t r = A.slot ? (size_t)A.slot[s] : s;
@@ -546,7 +547,7 @@ __device__ __forceinline__ double gp_tile_sample(const GpArgs &A, const GpLists 
     return total;
 }
 
-__device__ __forceinline__ int gp_walk_stream_mode(int mode, const GpArgs &A, const size_t s, const double *win) {
+MXG_DEV int gp_walk_stream_mode(int mode, const GpArgs &A, const size_t s, const double *win) {
     switch (mode) {
         case 0: return gp_walk_stream<0>(A, s, win);
         case 1: return gp_walk_stream<1>(A, s, win);

@@ -35,6 +35,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mxg_hd.h"
 #include "mxg_sincos.h"
 
 #define MXG_KURA_MEANFIELD 1
@@ -54,7 +55,7 @@ constexpr double kKuraTrust = 32.0;  // all |phase| <= 32: every difference is i
 struct KuraRed {
     double y, t, fn;
 };
-__device__ __forceinline__ KuraRed kura_reduce(double x) {
+MXG_DEV KuraRed kura_reduce(double x) {
     using namespace sincos_detail;
     KuraRed r;
     r.fn = rint(x * kInvPio2);
@@ -64,50 +65,50 @@ __device__ __forceinline__ KuraRed kura_reduce(double x) {
     r.t = fma(-r.fn, kPio2Lo2, (z - r.y) - w);
     return r;
 }
-__device__ __forceinline__ bool kura_rare(const KuraRed &r) { return fabs(r.y) < sincos_detail::kSmallRem && r.fn != 0.0; }
-__device__ __forceinline__ double kura_ksin(double y, double t) {
+MXG_DEV bool kura_rare(const KuraRed &r) { return fabs(r.y) < sincos_detail::kSmallRem && r.fn != 0.0; }
+MXG_DEV double kura_ksin(double y, double t) {
     using namespace sincos_detail;
     const double z = y * y, v = z * y;
-    const double r = fma_k(z, fma_k(z, fma_k(z, fma_kk(z, S6, S5), S4), S3), S2);
+    const double r = fma_k(z, fma_k(z, fma_k(z, fma_kk(z, S6, S5), S4), sincos_detail::S3), S2);  // (S3 qualified: mxg_scan.h has a struct of that name)
     return y - fma(-v, S1, fma(z, fma(-v, r, 0.5 * t), -t));
 }
-__device__ __forceinline__ double kura_kcos(double y, double t) {
+MXG_DEV double kura_kcos(double y, double t) {
     using namespace sincos_detail;
     const double z = y * y;
     const double r = z * fma_k(z, fma_k(z, fma_k(z, fma_k(z, fma_kk(z, C6, C5), C4), C3), C2), C1);
     const double hz = 0.5 * z, w = 1.0 - hz;
     return w + (((1.0 - w) - hz) + fma(z, r, -(y * t)));
 }
-__device__ __forceinline__ double kura_sin_of(const KuraRed &r) {
+MXG_DEV double kura_sin_of(const KuraRed &r) {
     const int n = (int)r.fn;
     const double s = kura_ksin(r.y, r.t), c = kura_kcos(r.y, r.t);
     const double v = (n & 1) ? c : s;
     return (n & 2) ? -v : v;
 }
-__device__ __forceinline__ double kura_cos_of(const KuraRed &r) {
+MXG_DEV double kura_cos_of(const KuraRed &r) {
     const int n = (int)r.fn;
     const double s = kura_ksin(r.y, r.t), c = kura_kcos(r.y, r.t);
     const double v = (n & 1) ? s : c;
     return ((n + 1) & 2) ? -v : v;
 }
 // the reduction of ONE argument that is known to lie in |x| <= 64
-__device__ __forceinline__ KuraRed kura_reduce_full(double x) {
+MXG_DEV KuraRed kura_reduce_full(double x) {
     KuraRed r = kura_reduce(x);
     if (kura_rare(r)) sincos_detail::reduce_accurate(x, r.y, r.t);
     return r;
 }
 // any argument
-__device__ __forceinline__ double kura_sin(double x) {
+MXG_DEV double kura_sin(double x) {
     if (!(fabs(x) <= 64.0)) return sin(x);
     return kura_sin_of(kura_reduce_full(x));
 }
-__device__ __forceinline__ double kura_cos(double x) {
+MXG_DEV double kura_cos(double x) {
     if (!(fabs(x) <= 64.0)) return cos(x);
     return kura_cos_of(kura_reduce_full(x));
 }
 
 // true on every lane when `c` holds on some lane of the wavefront; the host has one lane
-__device__ __forceinline__ bool kura_any(bool c) {
+MXG_DEV bool kura_any(bool c) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ballot_w64(c) != 0;
 #else
@@ -117,7 +118,7 @@ __device__ __forceinline__ bool kura_any(bool c) {
 
 // U sines of arguments in |x| <= 64, the rare accurate reduction behind one branch for all of them
 template <int U>
-__device__ __forceinline__ void kura_sin_group(const double (&x)[U], double (&s)[U]) {
+MXG_DEV void kura_sin_group(const double (&x)[U], double (&s)[U]) {
     KuraRed r[U];
     bool rare = false;
 #pragma unroll
@@ -137,7 +138,7 @@ __device__ __forceinline__ void kura_sin_group(const double (&x)[U], double (&s)
 // ---- maxiKuramotoOscillator::play: the sum over the gathered phases ----------------------------------------------------
 // TRUST: every g[j] - phase lies in |x| <= 64 (all |phases| <= kKuraTrust).  Same bits either way inside that domain.
 template <bool TRUST>
-__device__ __forceinline__ double kura_adj_exact(const double *g, int N, double phase) {
+MXG_DEV double kura_adj_exact(const double *g, int N, double phase) {
     double adj = 0;
     if constexpr (TRUST) {
         constexpr int U = kKuraUnroll;
@@ -159,7 +160,7 @@ __device__ __forceinline__ double kura_adj_exact(const double *g, int N, double 
 
 // mean field: one oscillator's sine and cosine ...
 template <bool TRUST>
-__device__ __forceinline__ void kura_sincos(double phase, double &s, double &c) {
+MXG_DEV void kura_sincos(double phase, double &s, double &c) {
     if (!TRUST && !(fabs(phase) <= 64.0)) {
         s = sin(phase);
         c = cos(phase);
@@ -173,7 +174,7 @@ __device__ __forceinline__ void kura_sincos(double phase, double &s, double &c) 
     c = ((n + 1) & 2) ? -vc : vc;
 }
 // ... and the sum from the set's sines and cosines: cos t_i * S - sin t_i * C, S and C in j order from 0.0
-__device__ __forceinline__ double kura_adj_meanfield(const double *sj, const double *cj, int N, double si, double ci) {
+MXG_DEV double kura_adj_meanfield(const double *sj, const double *cj, int N, double si, double ci) {
     double S = 0.0, C = 0.0;
     for (int j = 0; j < N; j++) {
         S += sj[j];
@@ -184,7 +185,7 @@ __device__ __forceinline__ double kura_adj_meanfield(const double *sj, const dou
 
 // The same sum in two steps, for a kernel in which one lane forms S and C and every lane of the set reads them (kernel K26):
 // exactly what kura_adj_meanfield gives -- j order, from 0.0.
-__device__ __forceinline__ void kura_meanfield_sums(const double *sj, const double *cj, int N, double &S, double &C) {
+MXG_DEV void kura_meanfield_sums(const double *sj, const double *cj, int N, double &S, double &C) {
     S = 0.0;
     C = 0.0;
     for (int j = 0; j < N; j++) {
@@ -192,10 +193,10 @@ __device__ __forceinline__ void kura_meanfield_sums(const double *sj, const doub
         C += cj[j];
     }
 }
-__device__ __forceinline__ double kura_meanfield_adj(double si, double ci, double S, double C) { return ci * S - si * C; }
+MXG_DEV double kura_meanfield_adj(double si, double ci, double S, double C) { return ci * S - si * C; }
 
 // the update line and the one wrap; returns what the oscillator's play() returns
-__device__ __forceinline__ double kura_advance(double phase, double dt, double freq, double K, int N, double adj) {
+MXG_DEV double kura_advance(double phase, double dt, double freq, double K, int N, double adj) {
     phase += dt * (freq + ((K / (double)N) * adj));
     if (phase >= MXG_TWOPI) phase -= MXG_TWOPI;
     else if (phase < 0) phase += MXG_TWOPI;
@@ -203,7 +204,7 @@ __device__ __forceinline__ double kura_advance(double phase, double dt, double f
 }
 
 // maxiKuramotoOscillatorSet::play's return value from the new phases
-__device__ __forceinline__ double kura_mix(const double *p, int N) {
+MXG_DEV double kura_mix(const double *p, int N) {
     double mix = 0.0;
     for (int i = 0; i < N; i++) mix += p[i];
     return mix / (double)N;
@@ -212,7 +213,7 @@ __device__ __forceinline__ double kura_mix(const double *p, int N) {
 // Where K is forced to 0 (an async set whose flag is down) the sum may be left out when the result is provably the same:
 // all arguments finite (here: inside the trusted domain) makes (0.0 / N) * adj a zero of either sign, and freq + (+-0.0) is
 // freq bit for bit unless freq is -0.0.
-__device__ __forceinline__ bool kura_zero_k_skippable(bool trusted, double freq) { return trusted && !(freq == 0.0 && signbit(freq)); }
+MXG_DEV bool kura_zero_k_skippable(bool trusted, double freq) { return trusted && !(freq == 0.0 && signbit(freq)); }
 
 }  // namespace
 }  // namespace mxg

@@ -16,10 +16,8 @@
 #else  // host build of the same text (accuracy test on the CPU)
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
-#define __device__
-#define __forceinline__ inline
 #endif
+#include "mxg_hd.h"
 
 namespace mxg {
 
@@ -30,10 +28,10 @@ constexpr double kLg1 = 6.666666666666735130e-01, kLg2 = 3.999999999940941908e-0
                  kLg7 = 1.479819860511658591e-01;
 constexpr double kSqrtHalf = 7.07106781186547524401e-01;
 
-__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+MXG_DEV double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // 1 / d for d in (1.7, 3.5): the hardware seed is good to ~24 bits; two Newton steps square the error twice
-__device__ __forceinline__ double recip(double d) {
+MXG_DEV double recip(double d) {
 #if defined(__HIPCC__)
     double r = __builtin_amdgcn_rcp(d);
 #else
@@ -46,14 +44,9 @@ __device__ __forceinline__ double recip(double d) {
 }  // namespace log_detail
 
 // log(x) for finite normal x > 0 (anything else: the generic routine)
-__device__ __forceinline__ double fast_log(double x) {
+MXG_DEV double fast_log(double x) {
     using namespace log_detail;
-    uint64_t bits;
-#if defined(__HIPCC__)
-    bits = (uint64_t)__double_as_longlong(x);
-#else
-    memcpy(&bits, &x, 8);
-#endif
+    const uint64_t bits = (uint64_t)__double_as_longlong(x);
     const uint32_t hi = (uint32_t)(bits >> 32);
     if (__builtin_expect(hi - 0x00100000u >= 0x7ff00000u - 0x00100000u, 0)) return log(x);  // zero, subnormal, negative, Inf, NaN
     // x = 2^k * m, m in [sqrt(1/2), sqrt(2)): fdlibm's exponent trick on the high word
@@ -63,12 +56,7 @@ __device__ __forceinline__ double fast_log(double x) {
     mh |= up ^ 0x3ff00000u;
     k += (int)(up >> 20);
     const uint64_t mbits = ((uint64_t)mh << 32) | (bits & 0xffffffffu);
-    double m;
-#if defined(__HIPCC__)
-    m = __longlong_as_double((long long)mbits);
-#else
-    memcpy(&m, &mbits, 8);
-#endif
+    const double m = __longlong_as_double((long long)mbits);
     const double f = m - 1.0;
     const double d = 2.0 + f;
     const double r = recip(d);

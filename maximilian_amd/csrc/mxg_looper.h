@@ -19,13 +19,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 #define MXG_LOOPER_PLAY_NONE (-1)  // no fused play head; the other two values are MXG_SMP_PLAY (0) and MXG_SMP_PLAYLOOP (2)
 #define MXG_LOOPER_MAX_N ((size_t)1 << 24)
@@ -42,7 +36,7 @@ struct LpRec {
 
 // H:708-710: the lag takes the enable as 0.0 / 1.0 (alpha 0.5, alphaReciprocal 0.5), then the clamp to the loop's start.
 // Returns whether the clamp moved the head.
-MXG_HOST_HD bool lp_rec_begin(LpRec &s, bool enabled, double start, size_t len) {
+MXG_HD bool lp_rec_begin(LpRec &s, bool enabled, double start, size_t len) {
     s.lag = (0.5 * (double)enabled) + (0.5 * s.lag);
     const double lo = start * (double)len;
     if (s.recpos < lo) {
@@ -53,12 +47,12 @@ MXG_HOST_HD bool lp_rec_begin(LpRec &s, bool enabled, double start, size_t len) 
 }
 
 // The element the head is on: (int)recordPosition inside [0, len), -1 outside (the departure; NaN and negatives included).
-MXG_HOST_HD long long lp_rec_index(double recpos, size_t len) {
+MXG_HD long long lp_rec_index(double recpos, size_t len) {
     return (recpos >= 0.0 && recpos < (double)len) ? (long long)recpos : -1;
 }
 
 // H:713-716: the element's old content and the input -> the element's new content
-MXG_HOST_HD double lp_rec_value(double current, double newSample, double recordMix, double lag) {
+MXG_HD double lp_rec_value(double current, double newSample, double recordMix, double lag) {
     const double currentSample = current / 32767.0;
     newSample = (recordMix * currentSample) + ((1.0 - recordMix) * newSample);
     newSample *= lag;
@@ -66,7 +60,7 @@ MXG_HOST_HD double lp_rec_value(double current, double newSample, double recordM
 }
 
 // H:718-720.  Returns whether the head went back to the loop's start.
-MXG_HOST_HD bool lp_rec_end(LpRec &s, double start, double end, size_t len) {
+MXG_HD bool lp_rec_end(LpRec &s, double start, double end, size_t len) {
     s.recpos += 1.0;
     if (s.recpos >= end * (double)len) {
         s.recpos = start * (double)len;
@@ -76,13 +70,13 @@ MXG_HOST_HD bool lp_rec_end(LpRec &s, double start, double end, size_t len) {
 }
 
 // (long long)x where x is anything: NaN and what lies below the range give a negative number, as the x86-64 conversion does
-MXG_HOST_HD long long lp_trunc(double x) { return (long long)fmin(fmax(x, -4.0e18), 4.0e18); }
+MXG_HD long long lp_trunc(double x) { return (long long)fmin(fmax(x, -4.0e18), 4.0e18); }
 
 // mxg_smp.h's smp_safe_head: unchanged on [-2, len + 2], pinned to it otherwise (NaN -> -2): the index stays in the guards
-MXG_HOST_HD double lp_safe_head(double pos, size_t len) { return fmin(fmax(pos, -2.0), (double)len + 2.0); }
+MXG_HD double lp_safe_head(double pos, size_t len) { return fmin(fmax(pos, -2.0), (double)len + 2.0); }
 
 // One call of play() (C:740-747) or playLoop(start, end) (C:960-967): advances `pos`, returns the index read (in [-2, len + 2]).
-MXG_HOST_HD long long lp_play_step(int mode, double &pos, double start, double end, size_t len) {
+MXG_HD long long lp_play_step(int mode, double &pos, double start, double end, size_t len) {
     if (mode == kLpPlay) {
         const long long idx = (long long)lp_safe_head(pos, len);
         pos += 1.0;
@@ -97,12 +91,12 @@ MXG_HOST_HD long long lp_play_step(int mode, double &pos, double start, double e
 }
 
 // ---- normalise (C:1126-1137) ---------------------------------------------------------------------------------------
-MXG_HOST_HD double lp_norm_max(double maxValue, double a) {  // a NaN element never passes the compare
+MXG_HD double lp_norm_max(double maxValue, double a) {  // a NaN element never passes the compare
     const double f = fabs(a);
     return f > maxValue ? f : maxValue;
 }
-MXG_HOST_HD float lp_norm_scale(double maxLevel, double maxValue) { return (float)(maxLevel / maxValue); }  // `float scale`: Inf at maxValue 0
-MXG_HOST_HD double lp_norm_apply(float scale, double a) { return round((double)scale * a); }
+MXG_HD float lp_norm_scale(double maxLevel, double maxValue) { return (float)(maxLevel / maxValue); }  // `float scale`: Inf at maxValue 0
+MXG_HD double lp_norm_apply(float scale, double a) { return round((double)scale * a); }
 
 // ---- one piece of one slot, as K25 cuts it (looper.hip) -------------------------------------------------------------------
 // A piece is at most a launch's samples of one slot.  Its entries lie `tile` apart (entry n at [n * tile]; the kernel keeps a
@@ -119,9 +113,9 @@ MXG_HOST_HD double lp_norm_apply(float scale, double a) { return round((double)s
 // first); where it fails (only outside the domain the reference is defined on) it searches idx[] backwards instead.
 constexpr int kLpLinkEn = 1, kLpLinkHead = 2;
 
-MXG_HOST_HD void lp_plan_slot(int N, int tile, size_t len, const double *enable, bool enable_all, double start, double end, int play_mode,
-                              double pstart, double pend, LpRec &rec, double &pos, uint32_t &drops, double *lag, int *idx, int *link,
-                              int *play) {
+MXG_HD void lp_plan_slot(int N, int tile, size_t len, const double *enable, bool enable_all, double start, double end, int play_mode,
+                         double pstart, double pend, LpRec &rec, double &pos, uint32_t &drops, double *lag, int *idx, int *link,
+                         int *play) {
     // runs of consecutive elements: the current one, the last complete one that is not the first, and the first
     int curBegin = 0, curFirst = -1, lastIdx = -1;
     int prevBegin = 0, prevFirst = 0, prevLen = -1;
@@ -191,7 +185,7 @@ MXG_HOST_HD void lp_plan_slot(int N, int tile, size_t len, const double *enable,
 
 // val[] holds the input on entry; every visit's entry receives the element's content once that sample is done.  c: the element's
 // content before the piece -> after it.  Returns whether a visit recorded (whether c must be stored).
-MXG_HOST_HD bool lp_walk_element(int n, int tile, double mix, double &c, double *val, const double *lag, const int *link) {
+MXG_HD bool lp_walk_element(int n, int tile, double mix, double &c, double *val, const double *lag, const int *link) {
     bool any = false;
     int m = n * tile, l = link[m];
     for (;;) {

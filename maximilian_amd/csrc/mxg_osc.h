@@ -4,22 +4,13 @@
 #pragma once
 #if defined(__HIPCC__)
 #include "mxg_common.h"
-#include "mxg_sincos.h"
 #else
 #include <math.h>
 #include <stddef.h>
 #include "../../include/maxigpu.h"
+#endif
+#include "mxg_hd.h"
 #include "mxg_sincos.h"
-namespace mxg {
-constexpr double kChandiv = 1.0;
-}
-#endif
-// MXG_STEP_HOST_CALLABLE (a -D of the translation unit, csrc/Makefile: drums.hip): these functions also run on its host pass
-#if defined(__HIPCC__) && defined(MXG_STEP_HOST_CALLABLE)
-#define MXG_OSC_HD __host__ __device__ __forceinline__
-#else
-#define MXG_OSC_HD __device__ __forceinline__
-#endif
 
 namespace mxg {
 namespace {
@@ -35,7 +26,7 @@ struct OscPre {
 };
 
 template <int WF>
-MXG_OSC_HD OscPre osc_pre(double f, double sr, double p1, double p2) {
+MXG_HD OscPre osc_pre(double f, double sr, double p1, double p2) {
     OscPre q;
     q.k = 0.0;
     q.p1 = p1;
@@ -70,7 +61,7 @@ MXG_OSC_HD OscPre osc_pre(double f, double sr, double p1, double p2) {
 // v_fract_f64, one instruction: x - floor(x) is x itself below 1 and the exact x - 1 from 1 to 2 (the instruction's clamp to the double
 // below 1.0 never acts on exact differences; a -0.0, which the subtraction would keep and fract would not, is excluded by the caller).
 template <bool UNIT = false>
-MXG_OSC_HD double wrap_at_one(double phase) {
+MXG_HD double wrap_at_one(double phase) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (UNIT) return __builtin_amdgcn_fract(phase);
     return phase - __hiloint2double(phase >= 1.0 ? 0x3FF00000 : 0, 0);
@@ -83,7 +74,7 @@ MXG_OSC_HD double wrap_at_one(double phase) {
 // FAST = false: the plain statement as hipcc compiles it (subtract, compare, two-word select) -- K1's sinebuf keeps it: that kernel is
 // bound by its store stream, and every leaner form of its loop measured SLOWER (profiles/r04_heavy_osc.md).
 template <bool FAST>
-MXG_OSC_HD double wrap_at_511(double phase) {
+MXG_HD double wrap_at_511(double phase) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (FAST) return phase - __hiloint2double(phase >= 511 ? 0x40800000 : 0, 0);
 #endif
@@ -112,8 +103,8 @@ constexpr int tab_copy() {
 constexpr int kSb4Copy = 520;     // sinebuf4 on the device: four copies of the 515-entry table this far apart (osc_tick; osc.hip load_tab)
 constexpr int kSineOddOff = 515;  // (odd and >= the table's 515 entries: element i of the second copy is 16-byte aligned for odd i; osc.hip asserts)
 template <int WF, bool TRUST = false, int FL = 0>
-MXG_OSC_HD double osc_tick(double &phase, double &hold, const OscPre &q,
-                                           const double *s_sine, const double *s_trans) {
+MXG_HD double osc_tick(double &phase, double &hold, const OscPre &q,
+                       const double *s_sine, const double *s_trans) {
     if constexpr (WF == MXG_OSC_SINEWAVE) {  // C:228-235
         double r = sin_2pi_phase<TRUST>(phase, s_sine, q.sk);
         hold = r;
@@ -264,7 +255,7 @@ struct OscPipe {
 };
 // (the K phase steps in two halves, for a caller that puts other instructions between them)
 template <int WF, int K, int HALF>
-MXG_OSC_HD void osc_pipe_phase_half(double &phase, const OscPre &q, OscPipe<K> &p) {
+MXG_HD void osc_pipe_phase_half(double &phase, const OscPre &q, OscPipe<K> &p) {
 #pragma unroll
     for (int i = HALF * (K / 2); i < (HALF + 1) * (K / 2); i++) {
         if constexpr (WF == MXG_OSC_SINEBUF) {
@@ -287,7 +278,7 @@ MXG_OSC_HD void osc_pipe_phase_half(double &phase, const OscPre &q, OscPipe<K> &
     }
 }
 template <int WF, int K>
-MXG_OSC_HD void osc_pipe_phase(double &phase, const OscPre &q, OscPipe<K> &p) {
+MXG_HD void osc_pipe_phase(double &phase, const OscPre &q, OscPipe<K> &p) {
     osc_pipe_phase_half<WF, K, 0>(phase, q, p);
     osc_pipe_phase_half<WF, K, 1>(phase, q, p);
 }
@@ -296,7 +287,7 @@ MXG_OSC_HD void osc_pipe_phase(double &phase, const OscPre &q, OscPipe<K> &p) {
 // FL bit 2 (a table without a copy, e.g. a voice's own): the second value is read at the first one's LDS address plus an 8 the optimizer
 // cannot see through -- one more integer addition per sample, but two ds_read_b64 instead of one ds_read2_b64 (see tab_copy).
 template <int WF, int K, int FL = kTickLean>
-MXG_OSC_HD void osc_pipe_fetch(OscPipe<K> &p, const double *s_tab) {
+MXG_HD void osc_pipe_fetch(OscPipe<K> &p, const double *s_tab) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr ((FL & 4) != 0) {
         typedef __attribute__((address_space(3))) const double lds_cd;
@@ -319,7 +310,7 @@ MXG_OSC_HD void osc_pipe_fetch(OscPipe<K> &p, const double *s_tab) {
     }
 }
 template <int WF, int K>
-MXG_OSC_HD void osc_pipe_finish(const OscPipe<K> &p, double (&r)[K], double &hold) {
+MXG_HD void osc_pipe_finish(const OscPipe<K> &p, double (&r)[K], double &hold) {
 #pragma unroll
     for (int i = 0; i < K; i++) {
         if constexpr (WF == MXG_OSC_SINEBUF)
@@ -334,8 +325,8 @@ MXG_OSC_HD void osc_pipe_finish(const OscPipe<K> &p, double (&r)[K], double &hol
 // FL: the table layout the caller's load_tab staged (bit 0, tab_copy: K1's sinebuf stages no copy and passes 0).  The staged form's phase
 // wrap is the three-instruction one whatever FL says: x - 0.0 is x, so its bits are the plain statement's (wrap_at_511).
 template <int WF, int K, int FL = kTickLean>
-MXG_OSC_HD void osc_tick_chunk(double &phase, double &hold, const OscPre &q, const double *s_sine,
-                                               const double *s_trans, double (&r)[K]) {
+MXG_HD void osc_tick_chunk(double &phase, double &hold, const OscPre &q, const double *s_sine,
+                           const double *s_trans, double (&r)[K]) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (osc_has_pipe<WF>()) {
         OscPipe<K> p;
@@ -355,8 +346,8 @@ MXG_OSC_HD void osc_tick_chunk(double &phase, double &hold, const OscPre &q, con
 // waveforms whose tick always overwrites `hold` it is left alone (a later tick sets it); square / pulse / impulse update
 // `hold` conditionally, so they run their (cheap) tick.
 template <int WF>
-MXG_OSC_HD void osc_skip(double &phase, double &hold, const OscPre &q, const double *s_sine,
-                                         const double *s_trans) {
+MXG_HD void osc_skip(double &phase, double &hold, const OscPre &q, const double *s_sine,
+                     const double *s_trans) {
     if constexpr (WF == MXG_OSC_SINEWAVE || WF == MXG_OSC_COSWAVE || WF == MXG_OSC_PHASOR || WF == MXG_OSC_TRIANGLE) {
         phase = wrap_at_one(phase);
         phase += q.inc;

@@ -24,20 +24,8 @@
 
 #include <type_traits>
 
+#include "mxg_hd.h"
 #include "mxg_sincos.h"
-
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
-#if defined(__HIPCC__)
-#define MXG_PB_MEMBER __host__ __device__ inline
-#else
-#define MXG_PB_MEMBER inline
-#endif
 
 // the reference's enum order (PolyBLEP.h, enum Waveform); include/maxigpu.h, where it is included, comes first and has them as an enum
 #ifndef MXG_PBLEP_WAVEFORMS
@@ -69,24 +57,24 @@ constexpr double kPbAmp = 1.0;                    // PolyBLEP::amplitude
 struct PbSinTab {
     const double *tab;
     SinTabK k;
-    MXG_PB_MEMBER double sin(double x) const { return sincos_tab<false>(x, tab, k); }
-    MXG_PB_MEMBER double cos(double x) const { return sincos_tab<true>(x, tab, k); }
+    MXG_HD double sin(double x) const { return sincos_tab<false>(x, tab, k); }
+    MXG_HD double cos(double x) const { return sincos_tab<true>(x, tab, k); }
 };
 
-MXG_HOST_HD double pb_sq(double x) { return x * x; }
+MXG_HD double pb_sq(double x) { return x * x; }
 
 // x -= (int64)x
-MXG_HOST_HD double pb_frac(double x) { return x - trunc(x); }
+MXG_HD double pb_frac(double x) { return x - trunc(x); }
 
 // P:43-51
-MXG_HOST_HD double pb_blep(double t, double dt) {
+MXG_HD double pb_blep(double t, double dt) {
     if (t < dt) return -pb_sq(t / dt - 1);
     if (t > 1 - dt) return pb_sq((t - 1) / dt + 1);
     return 0;
 }
 
 // P:54-64
-MXG_HOST_HD double pb_blamp(double t, double dt) {
+MXG_HD double pb_blamp(double t, double dt) {
     if (t < dt) {
         t = t / dt - 1;
         return ((-1 / 3.0) * pb_sq(t)) * t;
@@ -99,7 +87,7 @@ MXG_HOST_HD double pb_blamp(double t, double dt) {
 }
 
 // the triangle shared by tri / trap / trap2: y = 4 t folded at 1 and 3
-MXG_HOST_HD double pb_fold4(double t) {
+MXG_HD double pb_fold4(double t) {
     double y = t * 4;
     if (y >= 3) y -= 4;
     else if (y > 1) y = 2 - y;
@@ -108,11 +96,11 @@ MXG_HOST_HD double pb_fold4(double t) {
 
 // the fallback and SINE (P:162-164)
 template <class SC>
-MXG_HOST_HD double pb_sin(double t, const SC &sc) { return kPbAmp * sc.sin(kPbTwoPi * t); }
+MXG_HD double pb_sin(double t, const SC &sc) { return kPbAmp * sc.sin(kPbTwoPi * t); }
 
 // One waveform's get() below the fallback: t the phase, dt = freq / sr, pw the pulse width.
 template <int WF, class SC>
-MXG_HOST_HD double pb_wave(double t, double dt, double pw, const SC &sc) {
+MXG_HD double pb_wave(double t, double dt, double pw, const SC &sc) {
     if constexpr (WF == MXG_PBLEP_SINE) {
         return pb_sin(t, sc);
     } else if constexpr (WF == MXG_PBLEP_COSINE) {  // P:166-168
@@ -212,7 +200,7 @@ MXG_HOST_HD double pb_wave(double t, double dt, double pw, const SC &sc) {
 
 // maxiPolyBLEP::play(freq): the sample of the phase t, then t advanced (P:114-160)
 template <int WF, class SC>
-MXG_HOST_HD double pb_play(double &t, double freq, double sr, double pw, const SC &sc) {
+MXG_HD double pb_play(double &t, double freq, double sr, double pw, const SC &sc) {
     const double dt = freq / sr;
     double y;
     if (dt * sr >= sr / 4) y = pb_sin(t, sc);
@@ -223,7 +211,7 @@ MXG_HOST_HD double pb_play(double &t, double freq, double sr, double pw, const S
 }
 
 // PolyBLEP::sync (P:101-108): a negative phase wraps with t += 1 - (int64)t
-MXG_HOST_HD double pb_sync(double phase) { return phase >= 0 ? phase - trunc(phase) : phase + (1 - trunc(phase)); }
+MXG_HD double pb_sync(double phase) { return phase >= 0 ? phase - trunc(phase) : phase + (1 - trunc(phase)); }
 
 // a runtime waveform -> pb_play<WF> (host callers; the kernel is instantiated per waveform)
 template <class F>

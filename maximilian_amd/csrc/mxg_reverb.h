@@ -20,13 +20,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_RV_HD
-#if defined(__HIPCC__)
-#define MXG_RV_HD __host__ __device__ __forceinline__
-#else
-#define MXG_RV_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -37,62 +31,62 @@ constexpr int RV_MAX_FILTERS = 39;
 constexpr int RV_LP = 8;  // low-pass states per voice
 
 // ---- topology: delay lengths in samples (independent of the sample rate) --------------------------------------------
-MXG_RV_HD constexpr int rv_ncomb(int kind) { return kind == RV_SAT ? 4 : 8; }
-MXG_RV_HD constexpr int rv_nap(int kind) { return kind == RV_SAT ? 3 : kind == RV_FREEVERB ? 31 : 4; }
-MXG_RV_HD constexpr int rv_nfilt(int kind) { return rv_ncomb(kind) + rv_nap(kind); }
-MXG_RV_HD constexpr int rv_steps(int kind) { return kind == RV_STEREO ? 2 : 1; }  // allpass steps per sample
-MXG_RV_HD constexpr int rv_comb_len(int kind, int c) {
+MXG_HD constexpr int rv_ncomb(int kind) { return kind == RV_SAT ? 4 : 8; }
+MXG_HD constexpr int rv_nap(int kind) { return kind == RV_SAT ? 3 : kind == RV_FREEVERB ? 31 : 4; }
+MXG_HD constexpr int rv_nfilt(int kind) { return rv_ncomb(kind) + rv_nap(kind); }
+MXG_HD constexpr int rv_steps(int kind) { return kind == RV_STEREO ? 2 : 1; }  // allpass steps per sample
+MXG_HD constexpr int rv_comb_len(int kind, int c) {
     return kind == RV_SAT ? (c == 0 ? 778 : c == 1 ? 901 : c == 2 ? 1011 : 1123)
                           : (c == 0 ? 1557 : c == 1 ? 1617 : c == 2 ? 1491 : c == 3 ? 1422 : c == 4 ? 1277 : c == 5 ? 1356
                              : c == 6 ? 1188 : 1116);
 }
-MXG_RV_HD constexpr int rv_ap_len(int kind, int j) {
+MXG_HD constexpr int rv_ap_len(int kind, int j) {
     return kind == RV_SAT ? (j == 0 ? 125 : j == 1 ? 42 : 12)
                           : (j == 0 ? 225 : j == 1 ? 556 : j == 2 ? 441 : j == 3 ? 341 : 13 * (j + 1));
 }
 // filter f of a voice: the combs first, then the allpasses
-MXG_RV_HD constexpr int rv_len(int kind, int f) {
+MXG_HD constexpr int rv_len(int kind, int f) {
     return f < rv_ncomb(kind) ? rv_comb_len(kind, f) : rv_ap_len(kind, f - rv_ncomb(kind));
 }
-MXG_RV_HD constexpr int rv_off(int kind, int f) {  // first slot of filter f inside the voice's ring area
+MXG_HD constexpr int rv_off(int kind, int f) {  // first slot of filter f inside the voice's ring area
     int o = 0;
     for (int g = 0; g < f; g++) o += rv_len(kind, g);
     return o;
 }
-MXG_RV_HD constexpr int rv_ring_doubles(int kind) { return rv_off(kind, rv_nfilt(kind)); }
+MXG_HD constexpr int rv_ring_doubles(int kind) { return rv_off(kind, rv_nfilt(kind)); }
 static_assert(rv_ring_doubles(RV_SAT) == 3992 && rv_ring_doubles(RV_FREEVERB) == 18905 && rv_ring_doubles(RV_STEREO) == 12587,
               "ring state per voice");
 
 // ---- the per-sample arithmetic -----------------------------------------------------------------------------------
-MXG_RV_HD double rv_comb_plain(double d, double x) { return x + (0.85 * d); }
-MXG_RV_HD double rv_lowpass(double y, double cut, double d) { return y + (1.0 - cut) * (d - y); }
-MXG_RV_HD double rv_comb_lp(double x, double w, double y) { return x + (w * y); }
+MXG_HD double rv_comb_plain(double d, double x) { return x + (0.85 * d); }
+MXG_HD double rv_lowpass(double y, double cut, double d) { return y + (1.0 - cut) * (d - y); }
+MXG_HD double rv_comb_lp(double x, double w, double y) { return x + (w * y); }
 // one allpass step: `t` comes in as the stage's input and leaves as its output; returns what the ring slot gets
-MXG_RV_HD double rv_allpass(double d, double &t) {
+MXG_HD double rv_allpass(double d, double &t) {
     const double s = t + d * 0.85;
     t = d + (s * (-0.85));
     return s;
 }
-MXG_RV_HD double rv_clamp01(double v) {  // a NaN stays a NaN
+MXG_HD double rv_clamp01(double v) {  // a NaN stays a NaN
     if (v > 1.0) v = 1.0;
     if (v < 0.0) v = 0.0;
     return v;
 }
-MXG_RV_HD double rv_room_w(double roomsize) { return rv_clamp01((roomsize * 0.10) + 0.84); }
+MXG_HD double rv_room_w(double roomsize) { return rv_clamp01((roomsize * 0.10) + 0.84); }
 
 // ---- slot arithmetic of a time tile ------------------------------------------------------------------------------
 // A stored index outside its ring restarts at slot 0 (the reference cannot produce one).
-MXG_RV_HD int rv_idx_fix(int32_t idx, int D) { return (uint32_t)idx < (uint32_t)D ? idx : 0; }
+MXG_HD int rv_idx_fix(int32_t idx, int D) { return (uint32_t)idx < (uint32_t)D ? idx : 0; }
 // the slot of the k-th step after `idx`, 0 <= k <= D
-MXG_RV_HD int rv_slot(int idx, int k, int D) {
+MXG_HD int rv_slot(int idx, int k, int D) {
     const int s = idx + k;
     return s >= D ? s - D : s;
 }
 // the index after k >= 0 steps
-MXG_RV_HD int rv_idx_after(int idx, int k, int D) { return (idx + k) % D; }
+MXG_HD int rv_idx_after(int idx, int k, int D) { return (idx + k) % D; }
 // Samples a tile may take in one parallel pass over a ring of D slots stepped `steps` times per sample: the steps*L slots
 // they touch are distinct iff steps*L <= D.  (D >= steps for every ring here.)
-MXG_RV_HD constexpr int rv_sub_len(int D, int steps, int T) { return D / steps < T ? D / steps : T; }
+MXG_HD constexpr int rv_sub_len(int D, int steps, int T) { return D / steps < T ? D / steps : T; }
 
 // ---- one voice, one sample at a time, over the bank's state layout ---------------------------------------------------
 // rings [V][S] (voice-major, filter f at rv_off(kind, f)), idx int32 [V][F], lp [V][8], wc [V][2] = (w, cut).
@@ -109,7 +103,7 @@ struct RvArgs {
 };
 
 template <int KIND>
-MXG_RV_HD void rv_voice_ref(const RvArgs &A, size_t v) {
+MXG_HD void rv_voice_ref(const RvArgs &A, size_t v) {
     constexpr int NC = rv_ncomb(KIND), F = rv_nfilt(KIND), S = rv_ring_doubles(KIND);
     const size_t V = A.V, N = A.N;
     double *ring = A.rings + v * (size_t)S;

@@ -9,19 +9,11 @@
 //   void   X::up(src, d, dst)     dst[w] = src of lane(w) - d          (lanes below d: anything; never used)
 //   double X::from(src, j)        src of lane j                          (the same value in every slot)
 #pragma once
+#include "mxg_hd.h"
 
-#ifndef MXG_HD
-#if defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#else
-#define MXG_HD static inline
-#endif
-#endif
-#if defined(__HIPCC__)
-#define MXG_SCAN_MEMBER __device__ __forceinline__
+#if defined(__HIPCC__)  // (g++ -Wall warns about a pragma it does not know)
 #define MXG_SCAN_UNROLL _Pragma("unroll")
 #else
-#define MXG_SCAN_MEMBER inline
 #define MXG_SCAN_UNROLL
 #endif
 
@@ -41,7 +33,7 @@ constexpr int scan_nstate(int kind) { return kind == 0 || kind >= 3 ? 2 : 3; }  
 template <int KIND>
 struct ScanStep {
     double c[9];
-    MXG_SCAN_MEMBER double operator()(S3 &s, double x) const {
+    MXG_HD double operator()(S3 &s, double x) const {
         if constexpr (KIND == 0) {  // maxiDCBlocker: a = xm1, b = ym1
             s.b = x - s.a + c[0] * s.b;
             s.a = x;

@@ -30,6 +30,7 @@
 #pragma once
 #include <stddef.h>
 
+#include "mxg_hd.h"
 #include "mxg_scan.h"
 
 namespace mxg {
@@ -44,7 +45,7 @@ constexpr int scan_long_nstate(int kind) { return kind == 5 ? 1 : scan_nstate(ki
 template <>
 struct ScanStep<5> {
     double c[9];
-    MXG_SCAN_MEMBER double operator()(S3 &s, double x) const {
+    MXG_HD double operator()(S3 &s, double x) const {
         s.a = (c[0] * x) + (c[1] * s.a);
         return s.a;
     }

@@ -9,13 +9,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-#ifndef __device__
-#define __device__
 #endif
-#ifndef __forceinline__
-#define __forceinline__ inline
-#endif
-#endif
+#include "mxg_hd.h"
 #include "mxg_advance.h"
 
 namespace mxg {
@@ -42,8 +37,8 @@ struct SchedState {
 // A step the reference could not survive either -- NaN/Inf, or longer than the sample so that the single wrap of
 // maxiGrain::play (:219-224) leaves pos outside [0, len) and the reads go out of bounds -- is refused: failed = 5,
 // the grain is born with inc = 0 (it stays inside the buffer) and the launch reports MXG_ERR_INVALID.
-__device__ __forceinline__ void grain_birth(const SchedConst &c, double p01, const double grainSpeed,
-                                            double &pos0, double &inc, int &failed) {
+MXG_DEV void grain_birth(const SchedConst &c, double p01, const double grainSpeed,
+                         double &pos0, double &inc, int &failed) {
     p01 = 1.0 < p01 ? 1.0 : p01;  // max(min(1.0, .), 0.0)
     p01 = p01 < 0.0 ? 0.0 : p01;
     const double startPos = floor(c.dlen * p01);  // (unsigned long)(len*pos), pos >= 0
@@ -59,7 +54,7 @@ __device__ __forceinline__ void grain_birth(const SchedConst &c, double p01, con
 }
 
 // `randomOffset = rand() % 10` (:352 / :525) from the caller-supplied draws
-__device__ __forceinline__ void sched_draw(SchedState &q, const SchedConst &c, int &failed) {
+MXG_DEV void sched_draw(SchedState &q, const SchedConst &c, int &failed) {
     if (c.rnd) {
         if (q.cursor < c.R) q.randomOffset = (double)c.rnd[q.cursor]; else { failed = 2; q.randomOffset = 0; }
         q.cursor++;
@@ -71,8 +66,8 @@ __device__ __forceinline__ void sched_draw(SchedState &q, const SchedConst &c, i
 
 // modes 0/1: the body of `if (looper > cycleLength + randomOffset)` (:347-353 / :519-526)
 template <int MODE>
-__device__ __forceinline__ void sched_spawn01(SchedState &q, const SchedConst &c, double &pos0, double &inc,
-                                              int &failed) {
+MXG_DEV void sched_spawn01(SchedState &q, const SchedConst &c, double &pos0, double &inc,
+                           int &failed) {
     q.looper -= q.thr;
     const double grainSpeed = MODE == 0 ? (c.speed > 0 ? 1.0 : -1.0) : c.speed;  // :350
     grain_birth(c, (q.position / c.dlen) + c.pm, grainSpeed, pos0, inc, failed);
@@ -81,8 +76,8 @@ __device__ __forceinline__ void sched_spawn01(SchedState &q, const SchedConst &c
 
 // advances the scheduler by one sample; true if a grain (pos0, inc) is born at this sample
 template <int MODE>
-__device__ __forceinline__ bool sched_step(SchedState &q, const SchedConst &c, size_t n, double &pos0,
-                                           double &inc, int &failed) {
+MXG_DEV bool sched_step(SchedState &q, const SchedConst &c, size_t n, double &pos0,
+                        double &inc, int &failed) {
     if constexpr (MODE == 2) {
         q.looper += 1.0;
         double pos = c.a_ps[n * c.S];
@@ -123,10 +118,10 @@ __device__ __forceinline__ bool sched_step(SchedState &q, const SchedConst &c, s
 }
 
 template <int MODE>
-__device__ __forceinline__ SchedConst sched_const(size_t s, size_t S, size_t len, size_t R, const double *a,
-                                                  const double *b, const double *posMod, const int32_t *rnd,
-                                                  double cycleLength, double grainLength, double sr,
-                                                  int sampleDur) {
+MXG_DEV SchedConst sched_const(size_t s, size_t S, size_t len, size_t R, const double *a,
+                               const double *b, const double *posMod, const int32_t *rnd,
+                               double cycleLength, double grainLength, double sr,
+                               int sampleDur) {
     SchedConst c;
     c.dlen = (double)len;
     c.cycleLength = cycleLength;
@@ -148,8 +143,8 @@ __device__ __forceinline__ SchedConst sched_const(size_t s, size_t S, size_t len
 // Returns the number of samples it has consumed; the caller walks the rest one sample at a time with sched_step --
 // from a state that is, bit for bit, the one sched_step would have reached itself (tests/host_sched_events.cpp).
 template <int MODE, typename Record>
-__device__ __forceinline__ int sched_run_events(SchedState &q, const SchedConst &sc, int Tn, bool fast_enabled, int &failed,
-                                                Record record) {
+MXG_DEV int sched_run_events(SchedState &q, const SchedConst &sc, int Tn, bool fast_enabled, int &failed,
+                             Record record) {
     int nstart = 0;
     const double dlen = sc.dlen, rate = sc.rate;
     if constexpr (MODE <= 1) {

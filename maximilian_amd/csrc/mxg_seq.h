@@ -21,25 +21,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mxg_hd.h"
 #include "mxg_osc.h"  // the clock: maxiOsc::phasor's increment and recurrence
-
-#ifndef MXG_HD
-#if defined(__HIPCC__) && defined(MXG_STEP_HOST_CALLABLE)  // (csrc/Makefile: drums.hip runs these functions on its host pass too)
-#define MXG_HD __host__ __device__ __forceinline__
-#elif defined(__HIPCC__)
-#define MXG_HD __device__ __forceinline__
-#else
-#define MXG_HD static inline
-#endif
-#endif
-
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
 
 namespace mxg {
 namespace {
@@ -160,7 +143,7 @@ MXG_HD double seq_pulse(SeqPulse &p, double input, double holdTimeInSamples) {  
 }
 
 // One pattern's boundary table, the reference's operations in the reference's order (H:2172-2186); entries past len never fire.
-MXG_HOST_HD void seq_ratio_bounds(const double *times, int len, int L, double *norm) {
+MXG_HD void seq_ratio_bounds(const double *times, int len, int L, double *norm) {
     double sum = 0;
     for (int i = 0; i < len; i++) sum += times[i];
     double accumulatedTime = 0;

@@ -22,13 +22,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 #define MXG_SHAPE_HARDCLIP 0
 #define MXG_SHAPE_SOFTCLIP 1
@@ -44,24 +38,24 @@ namespace mxg {
 namespace {
 
 // ---- maxiNonlinearity ------------------------------------------------------------------------------------------------
-MXG_HOST_HD double shp_hardclip(double x) { return x >= 1 ? 1 : (x <= -1 ? -1 : x); }
+MXG_HD double shp_hardclip(double x) { return x >= 1 ? 1 : (x <= -1 ? -1 : x); }
 
-MXG_HOST_HD double shp_softclip(double x) {
+MXG_HD double shp_softclip(double x) {
     if (x >= 1) return 1;
     if (x <= -1) return -1;
     const double cube = (x * x) * x;  // the reference: pow(x, 3)
     return (2 / 3.0) * (x - cube / 3.0);
 }
 
-MXG_HOST_HD double shp_fastatan(double x) { return (x / (1.0 + 0.28 * (x * x))); }
+MXG_HD double shp_fastatan(double x) { return (x / (1.0 + 0.28 * (x * x))); }
 
-MXG_HOST_HD double shp_fastatandist(double in, double shape) { return (1.0 / shp_fastatan(shape)) * shp_fastatan(in * shape); }
+MXG_HD double shp_fastatandist(double in, double shape) { return (1.0 / shp_fastatan(shape)) * shp_fastatan(in * shape); }
 
 // 1.0 / atan(shape): the factor of atanDist
-MXG_HOST_HD double shp_atan_norm(double shape) { return 1.0 / atan(shape); }
-MXG_HOST_HD double shp_atandist(double in, double shape, double norm) { return norm * atan(in * shape); }
+MXG_HD double shp_atan_norm(double shape) { return 1.0 / atan(shape); }
+MXG_HD double shp_atandist(double in, double shape, double norm) { return norm * atan(in * shape); }
 
-MXG_HOST_HD double shp_asymclip(double x, double a, double b) {
+MXG_HD double shp_asymclip(double x, double a, double b) {
     if (x >= 1) x = 1;
     else if (x <= -1) x = -1;
     else if (x < 0) x = -(pow(-x, a));
@@ -71,7 +65,7 @@ MXG_HOST_HD double shp_asymclip(double x, double a, double b) {
 
 // one sample of `mode`; pa = shape / a, pb = the atanDist factor / b (unused ones are ignored)
 template <int MODE>
-MXG_HOST_HD double shp_apply(double x, double pa, double pb) {
+MXG_HD double shp_apply(double x, double pa, double pb) {
     if (MODE == MXG_SHAPE_HARDCLIP) return shp_hardclip(x);
     if (MODE == MXG_SHAPE_SOFTCLIP) return shp_softclip(x);
     if (MODE == MXG_SHAPE_FASTATAN) return shp_fastatan(x);
@@ -81,7 +75,7 @@ MXG_HOST_HD double shp_apply(double x, double pa, double pb) {
 }
 
 // ---- maxiXFade::xfade ------------------------------------------------------------------------------------------------
-MXG_HOST_HD void shp_xfade_gains(double xfader, double &g1, double &g2) {
+MXG_HD void shp_xfade_gains(double xfader, double &g1, double &g2) {
     const double lo = -1, hi = 1, omin = 0, omax = 1;
     xfader = xfader > hi ? hi : (xfader < lo ? lo : xfader);  // maxiMap::clamp
     double val = hi < xfader ? hi : xfader;                    // std::min(val, inMax)
@@ -90,11 +84,11 @@ MXG_HOST_HD void shp_xfade_gains(double xfader, double &g1, double &g2) {
     g1 = sqrt(1.0 - n);
     g2 = sqrt(n);
 }
-MXG_HOST_HD double shp_xfade(double ch1, double ch2, double g1, double g2) { return (ch1 * g1) + (ch2 * g2); }
+MXG_HD double shp_xfade(double ch1, double ch2, double g1, double g2) { return (ch1 * g1) + (ch2 * g2); }
 
 // ---- maxiSelect / maxiSelectX ----------------------------------------------------------------------------------------
 // the scaled and clamped index; *nan: the index was a NaN (taken as 0.0)
-MXG_HOST_HD double shp_select_index(double index, size_t K, bool normalised, bool *nan) {
+MXG_HD double shp_select_index(double index, size_t K, bool normalised, bool *nan) {
     if (normalised) index *= ((double)K - 1e-9);
     if (index < 0) index = 0;
     else if (index >= (double)K) index = (double)(K - 1);
@@ -102,15 +96,15 @@ MXG_HOST_HD double shp_select_index(double index, size_t K, bool normalised, boo
     return *nan ? 0.0 : index;
 }
 // maxiSelect: static_cast<size_t>(index)
-MXG_HOST_HD size_t shp_select_at(double index) { return (size_t)index; }
+MXG_HD size_t shp_select_at(double index) { return (size_t)index; }
 // maxiSelectX: a1 = floor(index), mix = index - a1, a2 = a1 + 1 wrapping to 0
-MXG_HOST_HD void shp_selectx_at(double index, size_t K, size_t &a1, size_t &a2, double &mix) {
+MXG_HD void shp_selectx_at(double index, size_t K, size_t &a1, size_t &a2, double &mix) {
     a1 = (size_t)floor(index);
     mix = index - (double)a1;
     a2 = a1 + 1;
     if (a2 == K) a2 = 0;
 }
-MXG_HOST_HD double shp_selectx_mix(double v1, double v2, double mix) { return (v1 * (1.0 - mix)) + (v2 * mix); }
+MXG_HD double shp_selectx_mix(double v1, double v2, double mix) { return (v1 * (1.0 - mix)) + (v2 * mix); }
 
 // ---- maxiLine --------------------------------------------------------------------------------------------------------
 struct LineState {
@@ -123,7 +117,7 @@ struct LinePar {
     bool oneShot, enable;
 };
 
-MXG_HOST_HD double shp_line(LineState &s, const LinePar &p, double trigger) {
+MXG_HD double shp_line(LineState &s, const LinePar &p, double trigger) {
     if (!s.complete) {
         if (p.enable && !(s.triggered != 0.0)) {
             s.triggered = (trigger > 0.0 && s.last <= 0.0) ? 1.0 : 0.0;
@@ -146,7 +140,7 @@ MXG_HOST_HD double shp_line(LineState &s, const LinePar &p, double trigger) {
 }
 
 // maxiLine::prepare: lineValue takes the PREVIOUS lineStart (the reference assigns it before lineStart changes)
-MXG_HOST_HD void shp_line_prepare(LineState &s, LinePar &p, double start, double end, double durationMs, bool isOneShot, double sampleRate) {
+MXG_HD void shp_line_prepare(LineState &s, LinePar &p, double start, double end, double durationMs, bool isOneShot, double sampleRate) {
     s.value = p.start;
     p.start = start;
     p.end = end;

@@ -29,15 +29,8 @@
 #include "mxg_common.h"
 #else  // host build of the same text: tests/host_sincos_accuracy.cpp measures the error bound on the CPU
 #include <math.h>
-#define __device__
-#define __forceinline__ inline
-#define MXG_TWOPI 6.283185307179586476925286766559
 #endif
-#if defined(__HIPCC__)
-#define MXG_SINCOS_HD __host__ __device__ __forceinline__
-#else
-#define MXG_SINCOS_HD inline
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 
@@ -61,29 +54,29 @@ constexpr double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-
 // first -- 17 moves next to the 9 FMAs of the two chains below, a fifth of sinewave's instructions at one wavefront per SIMD.
 // The coefficient goes in as the instruction's one scalar operand (`k`: wave-uniform, an SGPR pair set up outside the loop).
 #if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ double fma_k(double a, double b, double k) {  // a*b + k
+MXG_DEV double fma_k(double a, double b, double k) {  // a*b + k
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(k));
     return d;
 }
-__device__ __forceinline__ double fma_kk(double a, double k1, double k0) {  // a*k1 + k0
+MXG_DEV double fma_kk(double a, double k1, double k0) {  // a*k1 + k0
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(k1), "v"(k0));
     return d;
 }
 #else  // the host pass: sincos_tab below also runs on the host (mxg_polyblep_host)
-MXG_SINCOS_HD double fma_k(double a, double b, double k) { return fma(a, b, k); }
-MXG_SINCOS_HD double fma_kk(double a, double k1, double k0) { return fma(a, k1, k0); }
+MXG_HD double fma_k(double a, double b, double k) { return fma(a, b, k); }
+MXG_HD double fma_kk(double a, double k1, double k0) { return fma(a, k1, k0); }
 #endif
 
 // sin and cos of y + t on [-pi/4, pi/4] (t = tail of the reduced argument)
-__device__ __forceinline__ double k_sin(double y, double t) {
+MXG_DEV double k_sin(double y, double t) {
 #pragma clang fp contract(fast)
     const double z = y * y, v = z * y;
     const double r = fma_k(z, fma_k(z, fma_k(z, fma_kk(z, S6, S5), S4), S3), S2);
     return y - ((z * (0.5 * t - v * r) - t) - v * S1);
 }
-__device__ __forceinline__ double k_cos(double y, double t) {
+MXG_DEV double k_cos(double y, double t) {
 #pragma clang fp contract(fast)
     const double z = y * y;
     const double r = z * fma_k(z, fma_k(z, fma_k(z, fma_k(z, fma_kk(z, C6, C5), C4), C3), C2), C1);
@@ -91,7 +84,7 @@ __device__ __forceinline__ double k_cos(double y, double t) {
     return w + (((1.0 - w) - hz) + (z * r - y * t));
 }
 // x = k*pi/2 + (y + t), |y| <= pi/4 (+ a hair); valid for |x| <= 64
-__device__ __forceinline__ int reduce(double x, double &y, double &t) {
+MXG_DEV int reduce(double x, double &y, double &t) {
 #pragma clang fp contract(fast)
     const double fn = rint(x * kInvPio2);
     const double z = x - fn * kPio2Hi;  // exact: fn has <= 6 bits, kPio2Hi 33 bits
@@ -102,13 +95,13 @@ __device__ __forceinline__ int reduce(double x, double &y, double &t) {
 }
 // The same remainder to 151 bits of pi/2 (fdlibm's e_rem_pio2.c pieces): every fn*piece product is exact
 // (33 + 6 bits) and every subtraction is an error-free TwoSum, so y + t = x - fn*pi/2 to ~2^-150 absolute.
-__device__ __forceinline__ void two_diff(double a, double b, double &s, double &e) {
+MXG_DEV void two_diff(double a, double b, double &s, double &e) {
 #pragma clang fp contract(off)
     s = a - b;
     const double bb = a - s;  // the part of b that was actually subtracted
     e = (a - (s + bb)) + (bb - b);
 }
-__device__ __forceinline__ void reduce_accurate(double x, double &y, double &t) {
+MXG_DEV void reduce_accurate(double x, double &y, double &t) {
 #pragma clang fp contract(off)
     const double fn = rint(x * kInvPio2);
     const double r1 = x - fn * kPio2Hi;  // exact
@@ -121,7 +114,7 @@ __device__ __forceinline__ void reduce_accurate(double x, double &y, double &t) 
 }
 }  // namespace sincos_detail
 
-__device__ __forceinline__ double sin_small(double x) {
+MXG_DEV double sin_small(double x) {
     using namespace sincos_detail;
     if (!(fabs(x) <= 64.0)) return sin(x);
     double y, t;
@@ -131,7 +124,7 @@ __device__ __forceinline__ double sin_small(double x) {
     const double r = (n & 1) ? c : s;
     return (n & 2) ? -r : r;
 }
-__device__ __forceinline__ double cos_small(double x) {
+MXG_DEV double cos_small(double x) {
     using namespace sincos_detail;
     if (!(fabs(x) <= 64.0)) return cos(x);
     double y, t;
@@ -166,7 +159,7 @@ __device__ __forceinline__ double cos_small(double x) {
 struct SinTabK {
     double s120, c24;
 };
-__device__ __forceinline__ SinTabK sintab_k() {
+MXG_DEV SinTabK sintab_k() {
     SinTabK k = {1.0 / 120, 1.0 / 24};
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(k.s120), "+v"(k.c24));
@@ -177,7 +170,7 @@ __device__ __forceinline__ SinTabK sintab_k() {
 // (entries 0 .. 1024: the period and its repetition): no range test, no sign to restore, no index wrap.
 #define MXG_SINTAB_WIDE_LEN (4 * 1025)
 template <bool COS, bool TRUST = false>
-MXG_NO_CONTRACT MXG_SINCOS_HD double sincos_tab(double x, const double *tab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
+MXG_NO_CONTRACT MXG_HD double sincos_tab(double x, const double *tab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
     if constexpr (!TRUST)
         if (!(fabs(x) <= 64.0)) return COS ? cos(x) : sin(x);
     const double ax = TRUST ? x : fabs(x);
@@ -204,12 +197,12 @@ MXG_NO_CONTRACT MXG_SINCOS_HD double sincos_tab(double x, const double *tab, con
 }
 
 template <bool TRUST = false>
-__device__ __forceinline__ double sin_2pi_phase(double phase, const double *sintab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
+MXG_DEV double sin_2pi_phase(double phase, const double *sintab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
     double x = phase * (MXG_TWOPI);
     return sincos_tab<false, TRUST>(x, sintab, k);
 }
 template <bool TRUST = false>
-__device__ __forceinline__ double cos_2pi_phase(double phase, const double *sintab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
+MXG_DEV double cos_2pi_phase(double phase, const double *sintab, const SinTabK k = {1.0 / 120, 1.0 / 24}) {
     double x = phase * (MXG_TWOPI);
     return sincos_tab<true, TRUST>(x, sintab, k);
 }

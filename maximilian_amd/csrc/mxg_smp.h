@@ -6,13 +6,8 @@
 #else  // host build of the same text (tests/host_smp.cpp: the players against the oracle over wide parameter ranges)
 #include <math.h>
 #include <stddef.h>
-#define __host__
-#define __device__
-#define __forceinline__ inline
-namespace mxg {
-constexpr double kChandiv = 1.0;
-}
 #endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
@@ -30,7 +25,7 @@ constexpr int kSmpGuardLo = 4, kSmpGuardHi = 6 + kSmpWindow;
 
 // The head as the index computations see it: unchanged on [-2, len+2] (every position the reference is defined on),
 // pinned to that interval otherwise (NaN -> -2), so derived indices stay within [-4, len+4].
-__device__ __forceinline__ double smp_safe_head(double pos, size_t len) {
+MXG_DEV double smp_safe_head(double pos, size_t len) {
     return fmin(fmax(pos, -2.0), (double)len + 2.0);
 }
 
@@ -47,10 +42,10 @@ struct Smp {
 };
 
 // Modes 9-13 are a maxiTrigger::onZX test (H:569-579) in front of one of the plain players.
-__host__ __device__ constexpr int smp_base(int mode) {
+MXG_HD constexpr int smp_base(int mode) {
     return mode == 9 ? 1 : (mode == 10 || mode == 11) ? 5 : mode == 12 ? 6 : mode == 13 ? 0 : mode;
 }
-__host__ __device__ constexpr int smp_loads(int mode) {
+MXG_HD constexpr int smp_loads(int mode) {
     return mode == 14 ? 2 : (smp_base(mode) <= 3 ? 1 : (smp_base(mode) == 7 ? 4 : 2));
 }
 
@@ -70,8 +65,8 @@ struct SmpReq {
 };
 
 template <int MODE>
-__device__ __forceinline__ void smp_gen(Smp &s, double x, double t, double start, double end,
-                                        double sr, SmpReq<MODE> &q) {
+MXG_DEV void smp_gen(Smp &s, double x, double t, double start, double end,
+                     double sr, SmpReq<MODE> &q) {
     constexpr int B = smp_base(MODE);
     q.rem = 0.0;
     q.ok = true;
@@ -212,7 +207,7 @@ __device__ __forceinline__ void smp_gen(Smp &s, double x, double t, double start
 }
 
 template <int MODE>
-__device__ __forceinline__ double smp_eval(const SmpReq<MODE> &q, const double *val) {
+MXG_DEV double smp_eval(const SmpReq<MODE> &q, const double *val) {
     constexpr int B = smp_base(MODE);
     if constexpr (MODE == 14) {
         const double q2 = 1 - q.rem;

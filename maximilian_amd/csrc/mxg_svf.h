@@ -6,18 +6,12 @@
 // schedule, and that kernel's device listing is held fixed.
 #pragma once
 
-#ifndef MXG_HOST_HD
-#if defined(__HIPCC__)
-#define MXG_HOST_HD __host__ __device__ inline
-#else
-#define MXG_HOST_HD static inline
-#endif
-#endif
+#include "mxg_hd.h"
 
 namespace mxg {
 namespace {
 
-MXG_HOST_HD double svf_step(double &v0z, double &v1, double &v2, double x, const double (&c)[9]) {
+MXG_HD double svf_step(double &v0z, double &v1, double &v2, double x, const double (&c)[9]) {
     const double v1z = v1;
     const double v2z = v2;
     const double v3 = x + v0z - 2.0 * v2z;
