@@ -1235,6 +1235,59 @@ int mxg_convolve_bank_mac_host(size_t V, int bins, int R, const int *h_K, const 
                                float *h_ringR, float *h_ringI, int *h_head, float *h_pendR, float *h_pendI, const float *h_XR,
                                const float *h_XI, size_t nblocks, float *h_SR, float *h_SI);
 
+/* ---- maxiFFTBank / maxiIFFTBank: V streaming analysers / resynthesisers over the banks' blocks (kernel K29) ---- */
+/* maxiFFTBank(V) is V maxiFFT objects after setup(fftSize, hopSize, windowSize) (L/maxiFFT.cpp:45-60) fed in lock-step through
+ * process(float value) (:65-91).  A call takes d_in, double [N][V] (device) for any N >= 0; sample (n, v) enters stream v as
+ * (float)d_in[n][v], the conversion process(float) applies to a double argument.  State per stream: its last fftSize - hopSize
+ * floats (zeros after setup, :51) and the samples taken since the last frame, on the device; `fill` = pos - (windowSize - hopSize),
+ * 0 <= fill < hopSize, one counter for the bank, on the host (it depends only on the sequence of N values).
+ * A call emits F = (fill + N) / hopSize frames per stream: frame f of stream v is the buffer the reference transforms at its
+ * f-th `pos == windowSize` (:69) inside the call.  Outputs: real, imag, mags, phases, each fp32 [V * F][bins] (device), any of
+ * them NULL but not all -- the bits of mxg_fft_batch on that stream alone.  layout 0 = frame-major, row = f * V + v (concatenates
+ * across calls; what mxg_fft_features / mxg_mfcc_batch take); 1 = stream-major, row = v * F + f (what mxg_octave_batch takes).
+ * Two launches per call whatever V and N (gather, frames); no host round trip.  NOT capturable into a hipGraph, nor is
+ * mxg_ifft_bank_process: `fill` / `pos` and which of the two carry images is read advance on the host when a call is enqueued,
+ * so a replayed graph would read the image and the counter of the call it was captured from.  Bad arguments are refused, with a message that
+ * names the argument, before any device call: V = 0, an fftSize mxg_fft_plan_create refuses, windowSize above fftSize, hopSize
+ * outside [1, fftSize], null pointers. */
+typedef struct mxg_fft_bank mxg_fft_bank;
+mxg_fft_bank *mxg_fft_bank_create(size_t V, int fftSize, int hopSize, int windowSize);
+int mxg_fft_bank_destroy(mxg_fft_bank *b);
+int mxg_fft_bank_reset(mxg_fft_bank *b);     /* the state after setup */
+int mxg_fft_bank_pos(const mxg_fft_bank *b); /* fill */
+int mxg_fft_bank_process(mxg_fft_bank *b, const double *d_in, size_t N, int layout, float *d_real, float *d_imag, float *d_mags,
+                         float *d_phases, void *stream);
+
+/* maxiIFFTBank(V) is V maxiIFFT objects after setup(fftSize, hopSize, windowSize) (L/maxiFFT.cpp:141-152) called once per sample
+ * (:154-192).  A call produces d_out, double [N][V] (device), for any N: each float process() returns, widened exactly.  State
+ * per stream: buffer[fftSize] on the device (mxg_ifft_bank_buffer: [V][fftSize] as the reference would leave them); `pos` in
+ * [0, hopSize) for the bank, on the host.  A spectrum is consumed at every sample of the call where pos == 0 (:155): C points.
+ * input 0 = SPECTRUM: d_a = magnitudes, d_b = phases, as mxg_ifft_batch; 1 = cartesian: d_a = real, d_b = imag, with the
+ * as_reference = 0 meaning of mxg_ifft_batch_complex (the reference's COMPLEX mode, which transforms zeros, is not offered).
+ * Rows are fp32 [V * nrows][bins], nrows per stream, in either layout of mxg_fft_bank_process.
+ * row_mode 0 = direct: nrows = C, row j is consumed at point j.
+ * row_mode 1 = after-FFT: the per-sample loop of cpp/commandline/tests/ffttest/ffttest.cpp in lock-step with an mxg_fft_bank of
+ * the same hopSize created at the same time: nrows = the F rows that bank emitted for the same N.  Frame k completes at global
+ * sample k * hopSize + hopSize - 1 and is consumed at (k + 1) * hopSize, so with p = pos on entry point j takes row j when
+ * p > 0 and row j - 1 when p == 0; row -1 is the HELD spectrum, bank state [V][bins] x 2 that starts at zero (maxiFFT's
+ * magnitudes / phases after setup, :52-54) and becomes the last row passed after every after-FFT call that passed one.
+ * A wrong nrows is refused.  Launches per call: frames, overlap-add, and in after-FFT mode two device copies -- whatever V, N. */
+typedef struct mxg_ifft_bank mxg_ifft_bank;
+mxg_ifft_bank *mxg_ifft_bank_create(size_t V, int fftSize, int hopSize, int windowSize);
+int mxg_ifft_bank_destroy(mxg_ifft_bank *b);
+int mxg_ifft_bank_reset(mxg_ifft_bank *b);
+int mxg_ifft_bank_pos(const mxg_ifft_bank *b);
+const float *mxg_ifft_bank_buffer(const mxg_ifft_bank *b); /* device [V][fftSize]; valid until the next call on the bank */
+int mxg_ifft_bank_process(mxg_ifft_bank *b, int input, int row_mode, int layout, const float *d_a, const float *d_b, size_t nrows,
+                          size_t N, double *d_out, void *stream);
+
+/* Where a call of N samples puts its frames and consumption points: stateless, integer host code, the function both _process
+ * calls use (csrc/mxg_spectral_bank.h).  fft_fill / ifft_pos on entry (each in [0, hopSize)); *frames = F, *points = C,
+ * *first_is_held = 1 when after-FFT rows start at the held spectrum (ifft_pos == 0 and C > 0), *new_fill / *new_pos on exit.
+ * Any output pointer may be NULL. */
+int mxg_spectral_bank_plan_host(int fftSize, int hopSize, int windowSize, int fft_fill, int ifft_pos, size_t N, size_t *frames,
+                                size_t *points, int *first_is_held, int *new_fill, int *new_pos);
+
 /* ---- maxiMFCC batch --------------------------------------------------------------------- */
 /* maxiMFCC::setup(numBins, numFilters, numCoeffs, minFreq, maxFreq) (L/maxiMFCC.h:56-75): builds
  * the mel filterbank and DCT tables on the host libm.  Works without a device (tables only). */

@@ -2166,6 +2166,81 @@ private:
     maxigpu::DeviceArray<float> buffer_;
 };
 
+// V maxiFFT objects after setup(fftSize, hopSize, windowSize), fed in lock-step with what a bank rendered: double [N][V], any N,
+// any split into calls (mxg_fft_bank_*, kernel K29).  A call returns frames(N) frames per stream.
+class maxiFFTBank {
+public:
+    enum Layout { FRAME_MAJOR = 0, STREAM_MAJOR = 1 };  // row = f * V + v | row = v * F + f
+    maxiFFTBank(size_t V, int fftSize = 1024, int hopSize = 512, int windowSize = 0)
+        : V_(V), fftSize_(fftSize), hopSize_(hopSize), windowSize_(windowSize) {
+        h_ = mxg_fft_bank_create(V, fftSize, hopSize, windowSize);
+        if (!h_) throw std::runtime_error(std::string("mxg_fft_bank_create: ") + mxg_last_error());
+    }
+    maxiFFTBank(const maxiFFTBank &) = delete;
+    maxiFFTBank &operator=(const maxiFFTBank &) = delete;
+    ~maxiFFTBank() { mxg_fft_bank_destroy(h_); }
+    size_t voices() const { return V_; }
+    int getNumBins() const { return fftSize_ / 2; }
+    int pos() const { return mxg_fft_bank_pos(h_); }
+    // frames every stream completes inside the next call of N samples
+    size_t frames(size_t N) const {
+        size_t F = 0;
+        maxigpu::check(mxg_spectral_bank_plan_host(fftSize_, hopSize_, windowSize_, pos(), 0, N, &F, nullptr, nullptr, nullptr, nullptr),
+                       "mxg_spectral_bank_plan_host");
+        return F;
+    }
+    // d_in [N][V] -> fp32 [V * frames(N)][bins] outputs (any may be null, not all)
+    void process(const double *d_in, size_t N, float *d_mags, float *d_phases, float *d_real = nullptr, float *d_imag = nullptr,
+                 Layout layout = FRAME_MAJOR, void *stream = nullptr) {
+        maxigpu::check(mxg_fft_bank_process(h_, d_in, N, (int)layout, d_real, d_imag, d_mags, d_phases, stream), "mxg_fft_bank_process");
+    }
+    void reset() { maxigpu::check(mxg_fft_bank_reset(h_), "mxg_fft_bank_reset"); }
+
+private:
+    mxg_fft_bank *h_ = nullptr;
+    size_t V_;
+    int fftSize_, hopSize_, windowSize_;
+};
+
+// V maxiIFFT objects after setup(fftSize, hopSize, windowSize), called once per sample: rows of spectra -> double [N][V]
+// (mxg_ifft_bank_*, kernel K29).  DIRECT rows: one per consumption point, rows(N) of them.  AFTER_FFT rows: what a maxiFFTBank of
+// the same hop, created at the same time, returned for the same N -- the loop of ffttest.cpp, the last frame held across calls.
+class maxiIFFTBank {
+public:
+    enum Form { SPECTRUM = 0, CARTESIAN = 1 };
+    enum Rows { DIRECT = 0, AFTER_FFT = 1 };
+    maxiIFFTBank(size_t V, int fftSize = 1024, int hopSize = 512, int windowSize = 0) : V_(V), fftSize_(fftSize), hopSize_(hopSize) {
+        h_ = mxg_ifft_bank_create(V, fftSize, hopSize, windowSize);
+        if (!h_) throw std::runtime_error(std::string("mxg_ifft_bank_create: ") + mxg_last_error());
+    }
+    maxiIFFTBank(const maxiIFFTBank &) = delete;
+    maxiIFFTBank &operator=(const maxiIFFTBank &) = delete;
+    ~maxiIFFTBank() { mxg_ifft_bank_destroy(h_); }
+    size_t voices() const { return V_; }
+    int getNumBins() const { return fftSize_ / 2; }
+    int pos() const { return mxg_ifft_bank_pos(h_); }
+    // rows per stream the next call of N samples takes
+    size_t rows(size_t N, Rows mode = DIRECT) const {
+        size_t F = 0, C = 0;
+        maxigpu::check(mxg_spectral_bank_plan_host(fftSize_, hopSize_, 0, pos(), pos(), N, &F, &C, nullptr, nullptr, nullptr),
+                       "mxg_spectral_bank_plan_host");
+        return mode == AFTER_FFT ? F : C;
+    }
+    // d_a / d_b fp32 [V * rows(N, mode)][bins] (magnitudes / phases, or real / imag) -> d_out [N][V]
+    void process(const float *d_a, const float *d_b, size_t N, double *d_out, Form form = SPECTRUM, Rows mode = DIRECT,
+                 maxiFFTBank::Layout layout = maxiFFTBank::FRAME_MAJOR, void *stream = nullptr) {
+        maxigpu::check(mxg_ifft_bank_process(h_, (int)form, (int)mode, (int)layout, d_a, d_b, rows(N, mode), N, d_out, stream),
+                       "mxg_ifft_bank_process");
+    }
+    const float *buffers() const { return mxg_ifft_bank_buffer(h_); }  // device [V][fftSize]
+    void reset() { maxigpu::check(mxg_ifft_bank_reset(h_), "mxg_ifft_bank_reset"); }
+
+private:
+    mxg_ifft_bank *h_ = nullptr;
+    size_t V_;
+    int fftSize_, hopSize_;
+};
+
 class maxiMFCCBatch {
 public:
     ~maxiMFCCBatch() { if (plan_) mxg_mfcc_plan_destroy(plan_); }

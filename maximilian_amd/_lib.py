@@ -207,6 +207,18 @@ SIGNATURES = {
     "mxg_convolve_bank_play": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "mxg_convolve_bank_play_nv": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "mxg_convolve_bank_mac_host": (c_int, [c_size_t, c_int, c_int] + [c_void_p] * 11 + [c_size_t, c_void_p, c_void_p]),
+    "mxg_fft_bank_create": (c_void_p, [c_size_t, c_int, c_int, c_int]),
+    "mxg_fft_bank_destroy": (c_int, [c_void_p]),
+    "mxg_fft_bank_reset": (c_int, [c_void_p]),
+    "mxg_fft_bank_pos": (c_int, [c_void_p]),
+    "mxg_fft_bank_process": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_ifft_bank_create": (c_void_p, [c_size_t, c_int, c_int, c_int]),
+    "mxg_ifft_bank_destroy": (c_int, [c_void_p]),
+    "mxg_ifft_bank_reset": (c_int, [c_void_p]),
+    "mxg_ifft_bank_pos": (c_int, [c_void_p]),
+    "mxg_ifft_bank_buffer": (c_void_p, [c_void_p]),
+    "mxg_ifft_bank_process": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "mxg_spectral_bank_plan_host": (c_int, [c_int, c_int, c_int, c_int, c_int, c_size_t] + [c_void_p] * 5),
     "mxg_sampler_freq_host": (c_int, [c_size_t, c_void_p, c_size_t, c_void_p]),
     "mxg_sampler_render": (c_int, [c_size_t, c_size_t, c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 12),
     "mxg_fft_features": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),

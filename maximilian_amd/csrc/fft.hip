@@ -32,12 +32,25 @@
 #endif
 
 #include "mxg_spectral.h"
+#include "mxg_spectral_bank.h"
 
 namespace mxg {
 namespace {
 
 struct FftOut {
     float *real, *imag, *mags, *phases;
+};
+
+// Where frame f of a launch starts in `signal`.  The batch kernels take frames a uniform stride apart; the bank kernels (K29,
+// spectral_bank.hip) take frame f = a * D + b at a * sA + b * sB: hops along a stream's line one way, lines the other.  The bodies
+// are templates over either: the batch launches instantiate them with FrameUniform, one size_t where frame_stride was.
+struct FrameUniform {
+    size_t stride;
+    __device__ __forceinline__ size_t operator()(size_t f) const { return f * stride; }
+};
+struct FrameTwoLevel {
+    size_t D, sA, sB;
+    __device__ __forceinline__ size_t operator()(size_t f) const { return (f / D) * sA + (f % D) * sB; }
 };
 
 // compile-time output selection (bit 0 real, 1 imag, 2 mags, 3 phases): a statically known number
@@ -138,8 +151,9 @@ __device__ __forceinline__ void lds_stages(float2 *X, const int npts, const int 
 
 // ---- K6b: generic size -----------------------------------------------------------------------
 
+template <class Addr>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void fft_generic_kernel(
-    const float *__restrict__ signal, size_t frame_stride, size_t nframes, int fftSize, int numBits,
+    const float *__restrict__ signal, const Addr addr, size_t nframes, int fftSize, int numBits,
     const float *__restrict__ window, const float2 *__restrict__ tw, const float2 *__restrict__ post,
     FftOut out) {
     extern __shared__ float2 s_dyn[];
@@ -152,7 +166,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fft_generic_kernel(
     __syncthreads();
     auto P = [](int idx) { return idx + (idx >> 5); };  // one pad slot per 32: breaks pow-2 strides
     for (size_t f = (size_t)blockIdx.x * nwaves + wave; f < nframes; f += (size_t)gridDim.x * nwaves) {
-        const float *x = signal + f * frame_stride;
+        const float *x = signal + addr(f);
         for (int i = lane; i < half; i += 64) {
             float2 v;
             v.x = x[2 * i] * window[2 * i];          // calcFFT L/fft.cpp:501-503
@@ -219,9 +233,36 @@ __device__ __forceinline__ void ifft_frame(const float *__restrict__ m, const fl
     lds_stages(X, n, numBits, s_tw, 1, lane);
 }
 
-template <int INPUT>
-__global__ void ifft_generic_kernel(const float *__restrict__ mags, const float *__restrict__ phases,
-                                    size_t nframes, int n, int numBits, const float *__restrict__ window,
+// Which two rows of [bins] floats frame f of a launch transforms.  The batch launch takes row f of both blocks; the bank launch
+// (K29) takes frame f = v * C + j, consumption point j of stream v, from the row mxg_spectral_bank.h names: a row of the caller's
+// block in either layout, or stream v's held spectrum.
+struct RowsUniform {
+    const float *a, *b;
+    __device__ __forceinline__ void operator()(size_t f, size_t half, const float *&m, const float *&ph) const {
+        m = a + f * half;
+        ph = b + f * half;
+    }
+};
+struct RowsBank {
+    const float *a, *b, *heldA, *heldB;
+    size_t V, C, R;  // C points a stream this call, R rows a stream in the caller's block
+    int layout, after_fft, first_is_held;
+    __device__ __forceinline__ void operator()(size_t f, size_t half, const float *&m, const float *&ph) const {
+        const size_t v = f / C;
+        const long long r = spectral_bank_row(after_fft, first_is_held, f % C);
+        if (r < 0) {
+            m = heldA + v * half;
+            ph = heldB + v * half;
+        } else {
+            const size_t at = spectral_bank_row_index(layout, V, R, v, (size_t)r) * half;
+            m = a + at;
+            ph = b + at;
+        }
+    }
+};
+
+template <int INPUT, class Rows>
+__global__ void ifft_generic_kernel(const Rows rows, size_t nframes, int n, int numBits, const float *__restrict__ window,
                                     const float2 *__restrict__ tw, float *__restrict__ ifft_out) {
     extern __shared__ float2 s_dyn[];
     const int half = n >> 1;
@@ -234,7 +275,9 @@ __global__ void ifft_generic_kernel(const float *__restrict__ mags, const float 
     auto P = [](int idx) { return idx + (idx >> 5); };
     const float inv = 1.0f / (float)n;  // n is a power of two: x * inv is x / n, correctly rounded either way (L/fft.cpp:201-209 divides)
     for (size_t f = (size_t)blockIdx.x * nwaves + wave; f < nframes; f += (size_t)gridDim.x * nwaves) {
-        ifft_frame<INPUT>(mags + f * (size_t)half, phases + f * (size_t)half, n, numBits, s_tw, X, lane);
+        const float *m, *ph;
+        rows(f, (size_t)half, m, ph);
+        ifft_frame<INPUT>(m, ph, n, numBits, s_tw, X, lane);
         float *o = ifft_out + f * (size_t)n;
         for (int i = lane; i < n; i += 64) {
             const float r = X[P(i)].x * inv;  // L/fft.cpp:201-209
@@ -306,27 +349,7 @@ __global__ void ifft_stream_kernel(const float *__restrict__ mags, const float *
     }
 }
 
-// The hop buffer of maxiIFFT::process (L/maxiFFT.cpp:176-183): per frame, shift left by hop, zero the
-// tail, add the frame.  Position i of the buffer after frame k is therefore the left-to-right sum
-// (((carried or 0) + o_{m0}[..]) + ... ) + o_k[i] over the frames that overlap it, oldest first -- a closed
-// form each output sample can evaluate on its own, in the reference's order of additions.
-__device__ __forceinline__ float ola_value(const float *__restrict__ ifft_out, const float *__restrict__ buf_in,
-                                           long long k, int i, int n, int hop) {
-    // frames m = k - j contribute o_m[i + j*hop] while i + j*hop < n
-    const int J = (n - 1 - i) / hop;
-    float s;
-    long long m0 = k - J;
-    if (m0 <= 0) {  // the state carried into this launch is older than frame 0
-        const long long q = (long long)i + (k + 1) * hop;
-        s = (buf_in && q < n) ? buf_in[q] : 0.0f;
-        m0 = 0;
-    } else {
-        s = 0.0f;
-    }
-    for (long long mfr = m0; mfr <= k; mfr++) s += ifft_out[(size_t)mfr * n + (size_t)(i + (k - mfr) * hop)];
-    return s;
-}
-
+// (ola_value, the closed form of the hop buffer, lives in mxg_spectral.h: spectral_bank.hip evaluates it per stream)
 __global__ void ifft_ola_kernel(const float *__restrict__ ifft_out, size_t nframes, int n, int hop,
                                 const float *__restrict__ buf_in, float *__restrict__ out,
                                 float *__restrict__ buf_out) {
@@ -343,9 +366,9 @@ __global__ void ifft_ola_kernel(const float *__restrict__ ifft_out, size_t nfram
 
 
 // ---- K6a: fftSize 1024 (half = 512 = 8^3): LDS image, pad8 and round3 live in mxg_spectral.h ------------
-template <int OMASK, bool ALIGNED8>
+template <int OMASK, bool ALIGNED8, class Addr>
 __global__ __launch_bounds__(64 * kWavesPerBlock, MXG_FFT_MINWAVES) __attribute__((target("no-load-store-opt"))) void fft1024_kernel(
-    const float *__restrict__ signal, size_t frame_stride, size_t nframes,
+    const float *__restrict__ signal, const Addr addr, size_t nframes,
     const float *__restrict__ window, const float2 *__restrict__ tw, const float2 *__restrict__ post,
     FftOut out) {
     // one __shared__ object: [tw 512][post 256][X per wave]
@@ -379,7 +402,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, MXG_FFT_MINWAVES) __attribute_
     auto load_frame = [&](size_t fr, float2 (&dst)[8]) {
         // the frame index is wave-uniform: pin it to an SGPR so the row base is scalar arithmetic
         const unsigned fu = __builtin_amdgcn_readfirstlane((unsigned)(fr < nframes ? fr : nframes - 1));
-        const float *x = signal + (size_t)fu * frame_stride;
+        const float *x = signal + addr((size_t)fu);
 #pragma unroll
         for (int e = 0; e < 8; e++) {
             if constexpr (ALIGNED8) {
@@ -525,6 +548,70 @@ __global__ __launch_bounds__(64) void fft_features_kernel(const float *__restric
     }
 }
 }  // namespace
+}  // namespace mxg
+
+// ---- K29 frames (spectral_bank.hip): the launches of mxg_fft_batch / the two-kernel mxg_ifft_batch over the banks' addressing ----
+namespace mxg {
+
+int fft_bank_frames(const mxg_fft_plan *p, const float *d_lines, size_t D, size_t sA, size_t sB, size_t nrows, float *d_real,
+                    float *d_imag, float *d_mags, float *d_phases, hipStream_t st) {
+    FftOut out = {d_real, d_imag, d_mags, d_phases};
+    const FrameTwoLevel addr = {D, sA, sB};
+    size_t blocks = (nrows + kWavesPerBlock - 1) / kWavesPerBlock;
+    const size_t cap = 256 * 5;
+    if (blocks > cap) blocks = cap;
+    const int omask = (d_real ? 1 : 0) | (d_imag ? 2 : 0) | (d_mags ? 4 : 0) | (d_phases ? 8 : 0);
+    const bool fast_mask = omask == 3 || omask == 4 || omask == 12 || omask == 15;
+    const bool fast = p->fftSize == 1024 && !tune_get("fft_generic") && fast_mask;
+    KernelTimer kt(fast ? "fft1024_kernel<bank>" : "fft_generic_kernel<bank>", st);
+    if (fast) {
+        const bool aligned8 = (((uintptr_t)d_lines) & 7) == 0 && (sA & 1) == 0 && (sB & 1) == 0;
+#define MXG_FFT_LAUNCH(M, A)                                                                                 \
+    hipLaunchKernelGGL((fft1024_kernel<M, A, FrameTwoLevel>), dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, st, \
+                       d_lines, addr, nrows, p->d_window, p->d_tw, p->d_post, out)
+#define MXG_FFT_LAUNCH2(M) \
+    if (aligned8) MXG_FFT_LAUNCH(M, true); else MXG_FFT_LAUNCH(M, false)
+        switch (omask) {
+            case 3: MXG_FFT_LAUNCH2(3); break;
+            case 4: MXG_FFT_LAUNCH2(4); break;
+            case 12: MXG_FFT_LAUNCH2(12); break;
+            default: MXG_FFT_LAUNCH2(15); break;
+        }
+#undef MXG_FFT_LAUNCH2
+#undef MXG_FFT_LAUNCH
+    } else {
+        const int waves = p->fftSize <= 2048 ? kWavesPerBlock : (p->fftSize <= 4096 ? 2 : 1);  // as mxg_fft_batch
+        const size_t lds = sizeof(float2) * (waves * (size_t)(p->half + (p->half >> 5) + 1) + (size_t)p->half);
+        if (lds > 64 * 1024)
+            MXG_HIP(hipFuncSetAttribute((const void *)fft_generic_kernel<FrameTwoLevel>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        blocks = (nrows + waves - 1) / waves;
+        if (blocks > cap * (kWavesPerBlock / waves)) blocks = cap * (kWavesPerBlock / waves);
+        hipLaunchKernelGGL(fft_generic_kernel<FrameTwoLevel>, dim3((unsigned)blocks), dim3(64 * waves), lds, st, d_lines, addr, nrows,
+                           p->fftSize, p->numBits, p->d_window, p->d_tw, p->d_post, out);
+    }
+    return check_hip(hipGetLastError(), "fft bank kernel launch");
+}
+
+int ifft_bank_frames(const mxg_ifft_plan *p, int cartesian, const float *d_a, const float *d_b, const float *d_heldA,
+                     const float *d_heldB, int layout, int after_fft, int first_is_held, size_t V, size_t C, size_t R,
+                     float *d_ifft_out, hipStream_t st) {
+    const int n = p->fftSize;
+    const RowsBank rows = {d_a, d_b, d_heldA, d_heldB, V, C, R, layout, after_fft, first_is_held};
+    const size_t nframes = V * C;
+    const size_t per_wave = sizeof(float2) * (size_t)(n + (n >> 5) + 1);
+    const int waves = n <= 1024 ? 4 : (n <= 2048 ? 2 : 1);  // as the two-kernel form of mxg_ifft_batch
+    const size_t lds = per_wave * waves + sizeof(float2) * (size_t)n;
+    typedef void (*kern_t)(RowsBank, size_t, int, int, const float *, const float2 *, float *);
+    kern_t k = cartesian ? ifft_generic_kernel<1, RowsBank> : ifft_generic_kernel<0, RowsBank>;
+    if (lds > 64 * 1024) MXG_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    size_t blocks = (nframes + waves - 1) / waves;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    KernelTimer kt("ifft_generic_kernel<bank>", st);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * waves), lds, st, rows, nframes, n, p->numBits, p->d_window, p->d_tw,
+                       d_ifft_out);
+    return check_hip(hipGetLastError(), "ifft bank kernel launch");
+}
+
 }  // namespace mxg
 
 extern "C" {
@@ -674,8 +761,8 @@ int mxg_fft_batch(const mxg_fft_plan *p, const float *d_signal, size_t frame_str
     if (fast) {
         const bool aligned8 = (((uintptr_t)d_signal) & 7) == 0 && (frame_stride & 1) == 0;
 #define MXG_FFT_LAUNCH(M, A)                                                                            \
-    hipLaunchKernelGGL((fft1024_kernel<M, A>), dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, st, \
-                       d_signal, frame_stride, nframes, p->d_window, p->d_tw, p->d_post, out)
+    hipLaunchKernelGGL((fft1024_kernel<M, A, FrameUniform>), dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, st, \
+                       d_signal, FrameUniform{frame_stride}, nframes, p->d_window, p->d_tw, p->d_post, out)
 #define MXG_FFT_LAUNCH2(M) \
     if (aligned8) MXG_FFT_LAUNCH(M, true); else MXG_FFT_LAUNCH(M, false)
         switch (omask) {
@@ -691,11 +778,11 @@ int mxg_fft_batch(const mxg_fft_plan *p, const float *d_signal, size_t frame_str
         const int waves = p->fftSize <= 2048 ? kWavesPerBlock : (p->fftSize <= 4096 ? 2 : 1);
         const size_t lds = sizeof(float2) * (waves * (size_t)(p->half + (p->half >> 5) + 1) + (size_t)p->half);  // X per wave + stage twiddles
         if (lds > 64 * 1024)  // (8192 points: 33.8 KB + 32 KB)
-            MXG_HIP(hipFuncSetAttribute((const void *)fft_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            MXG_HIP(hipFuncSetAttribute((const void *)fft_generic_kernel<FrameUniform>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         blocks = (nframes + waves - 1) / waves;
         if (blocks > cap * (kWavesPerBlock / waves)) blocks = cap * (kWavesPerBlock / waves);
-        hipLaunchKernelGGL(fft_generic_kernel, dim3((unsigned)blocks), dim3(64 * waves), lds, st,
-                           d_signal, frame_stride, nframes, p->fftSize, p->numBits, p->d_window, p->d_tw,
+        hipLaunchKernelGGL(fft_generic_kernel<FrameUniform>, dim3((unsigned)blocks), dim3(64 * waves), lds, st,
+                           d_signal, FrameUniform{frame_stride}, nframes, p->fftSize, p->numBits, p->d_window, p->d_tw,
                            p->d_post, out);
     }
     return check_hip(hipGetLastError(), "fft kernel launch");
@@ -830,14 +917,15 @@ static int ifft_batch_impl(int input, const mxg_ifft_plan *p, const float *d_a, 
     const size_t per_wave = sizeof(float2) * (size_t)(n + (n >> 5) + 1);
     int waves = n <= 1024 ? 4 : (n <= 2048 ? 2 : 1);
     const size_t lds = per_wave * waves + sizeof(float2) * (size_t)n;  // + the stage twiddles
-    typedef void (*kern_t)(const float *, const float *, size_t, int, int, const float *, const float2 *, float *);
-    kern_t k = input == 0 ? ifft_generic_kernel<0> : (input == 1 ? ifft_generic_kernel<1> : ifft_generic_kernel<2>);
+    typedef void (*kern_t)(RowsUniform, size_t, int, int, const float *, const float2 *, float *);
+    kern_t k = input == 0 ? ifft_generic_kernel<0, RowsUniform>
+                          : (input == 1 ? ifft_generic_kernel<1, RowsUniform> : ifft_generic_kernel<2, RowsUniform>);
     if (lds > 64 * 1024) MXG_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     size_t blocks = (nframes + waves - 1) / waves;
     if (blocks > 256 * 8) blocks = 256 * 8;
     {
         KernelTimer kt("ifft_generic_kernel", st);
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * waves), lds, st, d_a, d_b, nframes, n, p->numBits, p->d_window,
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * waves), lds, st, RowsUniform{d_a, d_b}, nframes, n, p->numBits, p->d_window,
                            p->d_tw, io);
     }
     MXG_HIP(hipGetLastError());

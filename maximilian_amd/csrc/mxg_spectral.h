@@ -70,6 +70,18 @@ struct mxg_mfcc_plan {
     double *d_mmW, *d_mmD;
     std::vector<double> h_mmW, h_mmD;  // host copies (mxg_mfcc_plan_matrix_tables: the CPU suite replays the blocks with them)
 };
+namespace mxg {
+// The frame launches of kernel K29 (fft.hip, next to the transform bodies they instantiate; called by spectral_bank.hip).
+// fft_bank_frames: output row r = the transform of the fftSize floats at d_lines + (r / D) * sA + (r % D) * sB.
+// ifft_bank_frames: d_ifft_out [V][C][fftSize] = the windowed inverse transform of the row each (stream, consumption point)
+// takes by mxg_spectral_bank.h's rule, out of the caller's R rows per stream or the held spectrum [V][bins].
+int fft_bank_frames(const mxg_fft_plan *p, const float *d_lines, size_t D, size_t sA, size_t sB, size_t nrows, float *d_real,
+                    float *d_imag, float *d_mags, float *d_phases, hipStream_t st);
+int ifft_bank_frames(const mxg_ifft_plan *p, int cartesian, const float *d_a, const float *d_b, const float *d_heldA,
+                     const float *d_heldB, int layout, int after_fft, int first_is_held, size_t V, size_t C, size_t R,
+                     float *d_ifft_out, hipStream_t st);
+}  // namespace mxg
+
 constexpr int kMmPairs = 6, kMmCoefQuads = 4;
 constexpr int kFusedSlots = 8;
 constexpr int kFusedSlots16 = 16;
@@ -338,6 +350,28 @@ __device__ __forceinline__ bool exact_sqrtf4_try(const float (&x)[4], float (&r)
         r[i + 1] = q.y;
     }
     return worst >= 0x7F800000u - 0x0F800000u;
+}
+
+// The hop buffer of maxiIFFT::process (L/maxiFFT.cpp:176-183): per frame, shift left by hop, zero the
+// tail, add the frame.  Position i of the buffer after frame k is therefore the left-to-right sum
+// (((carried or 0) + o_{m0}[..]) + ... ) + o_k[i] over the frames that overlap it, oldest first -- a closed
+// form each output sample can evaluate on its own, in the reference's order of additions.  k = -1 (no frame
+// of this launch yet) is the carried buffer itself.
+__device__ __forceinline__ float ola_value(const float *__restrict__ ifft_out, const float *__restrict__ buf_in,
+                                           long long k, int i, int n, int hop) {
+    // frames m = k - j contribute o_m[i + j*hop] while i + j*hop < n
+    const int J = (n - 1 - i) / hop;
+    float s;
+    long long m0 = k - J;
+    if (m0 <= 0) {  // the state carried into this launch is older than frame 0
+        const long long q = (long long)i + (k + 1) * hop;
+        s = (buf_in && q < n) ? buf_in[q] : 0.0f;
+        m0 = 0;
+    } else {
+        s = 0.0f;
+    }
+    for (long long mfr = m0; mfr <= k; mfr++) s += ifft_out[(size_t)mfr * n + (size_t)(i + (k - mfr) * hop)];
+    return s;
 }
 
 // log-square of L/maxiMFCC.cpp:63

@@ -437,3 +437,126 @@ class maxiConvolveBank:
             self.close()
         except Exception:
             pass
+
+
+def spectral_bank_plan(fftSize, hopSize, windowSize, fft_fill, ifft_pos, N):
+    """mxg_spectral_bank_plan_host: what a call of N samples does to a maxiFFTBank at `fft_fill` and a maxiIFFTBank at `ifft_pos`
+    -> (frames, points, first_is_held, new_fill, new_pos).  Integer host code, no device."""
+    import ctypes
+    F, C = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    held, nf, npos = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    st = lib().mxg_spectral_bank_plan_host(int(fftSize), int(hopSize), int(windowSize), int(fft_fill), int(ifft_pos), int(N),
+                                           ctypes.addressof(F), ctypes.addressof(C), ctypes.addressof(held), ctypes.addressof(nf),
+                                           ctypes.addressof(npos))
+    if st < 0:
+        raise ValueError(lib().mxg_last_error().decode())
+    return F.value, C.value, held.value, nf.value, npos.value
+
+
+class maxiFFTBank:
+    """V maxiFFT objects after setup(fftSize, hopSize, windowSize), fed in lock-step (mxg_fft_bank_*, kernel K29).  `process(x)`
+    takes what a bank rendered, float64 [N, V] for any N, and returns the frames(N) frames every stream completes inside the call
+    as a dict of float32 [V * F, bins] DeviceBuffers (`want` names them: real / imag / mags / phases), rows frame-major
+    (layout 0: row = f * V + v) or stream-major (layout 1: row = v * F + f); state is carried between calls on the device."""
+    FRAME_MAJOR, STREAM_MAJOR = 0, 1
+
+    def __init__(self, V, fftSize=1024, hopSize=512, windowSize=0, stream=None):
+        self.h = None
+        self.stream = stream
+        h = lib().mxg_fft_bank_create(int(V), int(fftSize), int(hopSize), int(windowSize))
+        if not h:
+            raise ValueError(lib().mxg_last_error().decode())
+        self.h, self.V, self.fftSize, self.hopSize, self.windowSize, self.bins = h, int(V), fftSize, hopSize, windowSize, fftSize // 2
+
+    @property
+    def pos(self):
+        return lib().mxg_fft_bank_pos(self.h)
+
+    def frames(self, N):
+        return spectral_bank_plan(self.fftSize, self.hopSize, self.windowSize, self.pos, 0, N)[0]
+
+    def process(self, x, N=None, want=("mags", "phases"), layout=0):
+        if not (isinstance(x, DeviceBuffer) or hasattr(x, "data_ptr")):
+            x = DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float64))
+        N = int(np.prod(tuple(x.shape))) // self.V if N is None else int(N)
+        F = self.frames(N)
+        out = {k: DeviceBuffer((self.V * F, self.bins), np.float32, zero=False) for k in want}
+        check(lib().mxg_fft_bank_process(self.h, _ptr(x), N, int(layout), _ptr(out.get("real")), _ptr(out.get("imag")),
+                                         _ptr(out.get("mags")), _ptr(out.get("phases")), self.stream), "mxg_fft_bank_process")
+        self._keep = x
+        return out
+
+    def reset(self):
+        check(lib().mxg_fft_bank_reset(self.h), "mxg_fft_bank_reset")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mxg_fft_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class maxiIFFTBank:
+    """V maxiIFFT objects after setup(fftSize, hopSize, windowSize), called once per sample (mxg_ifft_bank_*, kernel K29).
+    `process(a, b, N)` returns float64 [N, V], the layout the banks speak.  form SPECTRUM: a = magnitudes, b = phases; CARTESIAN:
+    a = real, b = imag.  Rows are float32 [V * nrows, bins] in either layout of maxiFFTBank.  rows DIRECT: one row per consumption
+    point, rows(N) of them; AFTER_FFT: the rows a maxiFFTBank of the same hop, created at the same time, returned for the same N
+    (the per-sample loop of ffttest.cpp: a point takes the last frame completed before it, held across calls)."""
+    SPECTRUM, CARTESIAN = 0, 1
+    DIRECT, AFTER_FFT = 0, 1
+
+    def __init__(self, V, fftSize=1024, hopSize=512, windowSize=0, stream=None):
+        self.h = None
+        self.stream = stream
+        h = lib().mxg_ifft_bank_create(int(V), int(fftSize), int(hopSize), int(windowSize))
+        if not h:
+            raise ValueError(lib().mxg_last_error().decode())
+        self.h, self.V, self.fftSize, self.hopSize, self.windowSize, self.bins = h, int(V), fftSize, hopSize, windowSize, fftSize // 2
+
+    @property
+    def pos(self):
+        return lib().mxg_ifft_bank_pos(self.h)
+
+    def rows(self, N, rows=0):
+        """Rows per stream a call of N samples takes."""
+        p = self.pos
+        F, C = spectral_bank_plan(self.fftSize, self.hopSize, 0, p, p, N)[:2]
+        return F if rows == self.AFTER_FFT else C
+
+    def process(self, a, b, N, form=0, rows=0, layout=0, out=None):
+        nrows = self.rows(N, rows)
+        if nrows:
+            a = a if isinstance(a, DeviceBuffer) or hasattr(a, "data_ptr") else DeviceBuffer.from_numpy(np.ascontiguousarray(a, np.float32))
+            b = b if isinstance(b, DeviceBuffer) or hasattr(b, "data_ptr") else DeviceBuffer.from_numpy(np.ascontiguousarray(b, np.float32))
+            assert int(np.prod(tuple(a.shape))) == self.V * nrows * self.bins, "V * rows(N) rows of bins values"
+        out = out if out is not None else DeviceBuffer((int(N), self.V), np.float64, zero=False)
+        check(lib().mxg_ifft_bank_process(self.h, int(form), int(rows), int(layout), _ptr(a) if nrows else None,
+                                          _ptr(b) if nrows else None, nrows, int(N), _ptr(out), self.stream), "mxg_ifft_bank_process")
+        self._keep = (a, b)
+        return out
+
+    def buffers(self):
+        """The V carried buffers, float32 [V, fftSize], as the reference's objects would hold them."""
+        check(lib().mxg_sync(), "mxg_sync")
+        out = np.empty((self.V, self.fftSize), np.float32)
+        check(lib().mxg_memcpy_d2h(out.ctypes.data, lib().mxg_ifft_bank_buffer(self.h), out.nbytes, None), "mxg_memcpy_d2h")
+        return out
+
+    def reset(self):
+        check(lib().mxg_ifft_bank_reset(self.h), "mxg_ifft_bank_reset")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mxg_ifft_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
