@@ -13,12 +13,18 @@
 // arithmetic; a later change of the sample rate does nothing to an existing object, and a copy keeps its source's lengths.  Its
 // rings (32 312 doubles at 44 100 Hz) are allocated at the first call.  The reference's 3 100-slot pre-delay ring is not carried:
 // its output is used by nothing and no call can observe it.  A sample rate the kernel does not accept (outside 3 345 ..
-// 295 129 Hz) prints one line and plays silence.  The helper class maxiReverbFilters is not provided.
+// 295 129 Hz) prints one line and plays silence.
+// maxiReverbFilters, the helper class a patch builds its own reverb from, is a host value type over the per-object part of the
+// step header the network kernel K30 shares (maximilian_amd/csrc/mxg_revfilt_obj.h, which must lie beside include/ as it does in
+// this tree): no device call per sample.  Banks of many voices of such a network run on the device (maxiReverbNetBank in
+// maximilian_bank.hpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
+#include "../maximilian_amd/csrc/mxg_revfilt_obj.h"
 #include "maximilian.h"
 
 namespace maxigpu {
@@ -174,6 +180,42 @@ class maxiFreeVerbStereo {
 };
 
 #undef MAXIGPU_REVERB_VALUE_TYPE
+
+// The reference's 14 public methods with its signatures and its constructor state: a ring of 44 100 zeros, feedback 0.8,
+// gain_cof 0.85, index 0.  The object keeps the whole ring, so a size that grows or shrinks mid-stream behaves like the
+// reference for as long as the reference stays inside its ring; an index, a tapdpos position or a tap that would leave the
+// 44 100 slots reads 0.0 and stores nothing (the reference reads and writes outside its valarray there).  setlength is declared
+// by the reference and defined nowhere; here it sets the length that gettap wraps at until the next call sets its own.
+class maxiReverbFilters {
+public:
+    maxiReverbFilters() : delay_line(mxg::RF_RING, 0.0) {}
+    double twopoint(double input) { return mxg::rf_obj_twopoint(s, input); }
+    double comb1(double input, double size) { return mxg::rf_obj_comb1(s, delay_line.data(), input, size); }
+    double combff(double input, double size) { return mxg::rf_obj_combff(s, delay_line.data(), input, size); }
+    double combfb(double input, double size, double fb) { return mxg::rf_obj_combfb(s, delay_line.data(), input, size, fb); }
+    double lpcombfb(double input, double size, double fb, double cutoff) {
+        return mxg::rf_obj_lpcombfb(s, delay_line.data(), input, size, fb, cutoff);
+    }
+    double allpass(double input, double size) { return mxg::rf_obj_allpass(s, delay_line.data(), input, size, s.gain_cof); }
+    double allpass(double input, double size, double fback) { return mxg::rf_obj_allpass(s, delay_line.data(), input, size, fback); }
+    double allpasstap(double input, double size, int tap) { return mxg::rf_obj_allpasstap(s, delay_line.data(), input, size, tap); }
+    void setlength(int length) { s.delay_size = length; }
+    double onetap(double input, double size) { return mxg::rf_obj_onetap(s, delay_line.data(), input, size); }
+    double tapd(double input, double size, double *taps, int numtaps) {
+        return mxg::rf_obj_tapd(s, delay_line.data(), input, size, taps, numtaps);
+    }
+    double tapdwgain(double input, double size, double *taps, int numtaps, double *gain) {
+        return mxg::rf_obj_tapdwgain(s, delay_line.data(), input, size, taps, numtaps, gain);
+    }
+    double tapdpos(double input, int size, int *taps, int numtaps) {
+        return mxg::rf_obj_tapdpos(s, delay_line.data(), input, size, taps, numtaps);
+    }
+    double gettap(int tap) { return mxg::rf_obj_gettap(s, delay_line.data(), tap); }
+
+private:
+    std::vector<double> delay_line;
+    mxg::RfState s;
+};
 
 class maxiDattaroReverb {
     maxigpu::ps::DattaroLine line_;  // (captures maxiSettings::sampleRate)

@@ -553,6 +553,33 @@ int mxg_dattaro_layout_host(uint32_t sample_rate, uint32_t *lengths, uint32_t *o
 int mxg_dattaro_render(uint32_t sample_rate, size_t V, size_t N, const double *d_in, double *d_rings, int32_t *d_idx,
                        double *d_state, double *d_out, void *stream);
 
+/* ---- custom reverb networks out of maxiReverbFilters stages (libs/maxiReverb.h:42-73, K30) ---------------------------
+ * A bank of V reverbs that share one topology the caller chooses: n_combs parallel feedback combs summed in order, then
+ * n_allpasses serial allpasses, each count in [0, MXG_REVNET_MAX_STAGES], their sum at least 1.  Per sample and voice:
+ *   acc = 0.0; acc += comb_c(x) for c = 0 .. n_combs - 1;  t = acc (t = x without combs);  t = allpass_a(t) in order;  out = t
+ * where comb c is maxiReverbFilters::combfb(x, size, fb), or lpcombfb(x, size, fb, cutoff) where comb_lowpass[c] != 0
+ * (comb_lowpass may be NULL: every comb plain), and allpass a is allpass(x, size, fb).  The sizes are host arrays of
+ * integer lengths in samples, [1, 44100] (the reference's ring); they are per bank and must accompany it for its whole
+ * life.  A low-pass comb must be at least 64 samples long; plain combs and allpasses may have any length from 1.
+ * mxg_revnet_layout_host needs no device: it checks a topology (MXG_ERR_INVALID and a message otherwise) and answers
+ * offsets [n_combs + n_allpasses] (stage f's first slot inside the voice's ring area, combs first) and the ring doubles
+ * per voice, the sum of the lengths (either output may be NULL).
+ * Parameters, device arrays, per voice and stage, constant within a call and free to change between calls; nothing
+ * clamps them, as nothing does in the reference: d_comb_fb [V][n_combs], d_comb_cut [V][n_combs] (read for low-pass combs
+ * only; NULL allowed without one), d_ap_fb [V][n_allpasses].
+ * Carried state, caller-owned device memory, all zero for fresh objects: d_rings [V][ring_doubles] (VOICE-major; stage f of
+ * voice v at d_rings[v * ring_doubles + offsets[f]]), d_idx int32 [V][n_combs + n_allpasses] (the ring indices; one
+ * outside its ring restarts at slot 0), d_lp [V][n_combs] (the low-pass combs' filter states; NULL allowed without one).
+ * d_in and d_out are [N][V], any N, any V, any split of a stream into calls.
+ * Bit-exact (+ - * only, contraction off, subnormals kept): outputs and every piece of state.  No CPU fallback. */
+#define MXG_REVNET_MAX_STAGES 32
+int mxg_revnet_layout_host(uint32_t n_combs, uint32_t n_allpasses, const uint32_t *comb_sizes, const uint32_t *ap_sizes,
+                           const uint32_t *comb_lowpass, uint32_t *offsets, uint32_t *ring_doubles);
+int mxg_revnet_render(uint32_t n_combs, uint32_t n_allpasses, const uint32_t *comb_sizes, const uint32_t *ap_sizes,
+                      const uint32_t *comb_lowpass, size_t V, size_t N, const double *d_in, const double *d_comb_fb,
+                      const double *d_comb_cut, const double *d_ap_fb, double *d_rings, int32_t *d_idx, double *d_lp,
+                      double *d_out, void *stream);
+
 /* ---- sequencers: maxiRatioSeq / maxiStep / maxiCounter / maxiIndex / maxiZXToPulse / maxiTrigger::onZX (K15) ---------
  * (H:564-596, 1953-2013, 2093-2262.)  Compares, + - / floor and integer indexing only: every output and every state array is
  * BIT-EXACT.  The one departure: a table read index is held inside its table where the reference would index out of bounds

@@ -642,6 +642,82 @@ private:
     maxigpu::DeviceArray<double> state_;
 };
 
+// ---- custom reverb networks out of maxiReverbFilters stages (libs/maxiReverb.h:42-73, K30) ----------------------------------
+// One topology per bank: the parallel combs `combSizes` summed in order -- combfb, or lpcombfb where `combLowpass` flags it
+// (empty: every comb plain) -- into the serial allpasses `apSizes`.  Lengths are whole samples in [1, 44100], at most 32 of each
+// kind, a low-pass comb at least 64 (mxg_revnet_layout_host; a topology it does not accept throws).  Feedbacks and cutoffs are
+// per voice and stage, constant within a call; nothing clamps them.  Rings voice-major, everything zeroed like fresh objects.
+class maxiReverbNetBank {
+public:
+    maxiReverbNetBank(size_t voices, const std::vector<uint32_t> &combSizes, const std::vector<uint32_t> &apSizes,
+                      const std::vector<uint32_t> &combLowpass = {}, double combFb = 0.85, double combCut = 0.2, double apFb = 0.85)
+        : V(voices), lay_(combSizes, apSizes, combLowpass), rings_(voices * lay_.S), idx_(voices * lay_.F() + 1), lp_(voices * lay_.P() + 1),
+          cfb_(voices * lay_.P() + 1), cut_(voices * lay_.P() + 1), afb_(voices * lay_.A() + 1) {
+        setCombFb(combFb);
+        setCombCut(combCut);
+        setApFb(apFb);
+    }
+    // d_in, d_out [N][V]
+    void play(size_t N, const double *d_in, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_revnet_render((uint32_t)lay_.P(), (uint32_t)lay_.A(), lay_.combs.data(), lay_.aps.data(), lay_.lowp.data(), V, N, d_in,
+                                         cfb_.get(), cut_.get(), afb_.get(), rings_.get(), idx_.get(), lp_.get(), d_out, stream),
+                       "mxg_revnet_render");
+    }
+    // one value for every voice and stage, or host values [V][stages]; call between blocks (the call waits for the device)
+    void setCombFb(double fb) { fill(cfb_, lay_.P(), fb); }
+    void setCombCut(double cutoff) { fill(cut_, lay_.P(), cutoff); }
+    void setApFb(double fb) { fill(afb_, lay_.A(), fb); }
+    void setCombFb(const std::vector<double> &fb) { put(cfb_, lay_.P(), fb); }
+    void setCombCut(const std::vector<double> &cutoff) { put(cut_, lay_.P(), cutoff); }
+    void setApFb(const std::vector<double> &fb) { put(afb_, lay_.A(), fb); }
+    void clear() {  // fresh objects again; the parameters stay
+        maxigpu::check(mxg_sync(), "mxg_sync");
+        maxigpu::check(mxg_memset(rings_.get(), 0, rings_.size() * sizeof(double), nullptr), "mxg_memset");
+        maxigpu::check(mxg_memset(idx_.get(), 0, idx_.size() * sizeof(int32_t), nullptr), "mxg_memset");
+        maxigpu::check(mxg_memset(lp_.get(), 0, lp_.size() * sizeof(double), nullptr), "mxg_memset");
+        maxigpu::check(mxg_stream_sync(nullptr), "mxg_stream_sync");
+    }
+    size_t combs() const { return lay_.P(); }
+    size_t allpasses() const { return lay_.A(); }
+    uint32_t ringDoubles() const { return lay_.S; }                     // per voice
+    const std::vector<uint32_t> &offsets() const { return lay_.off; }   // [combs + allpasses], combs first
+    double *rings() { return rings_.get(); }                            // device [V][ringDoubles()]
+    int32_t *indices() { return idx_.get(); }                           // device [V][combs + allpasses]
+    double *lowpassStates() { return lp_.get(); }                       // device [V][combs]
+    double *combFb() { return cfb_.get(); }                             // device [V][combs]
+    double *combCut() { return cut_.get(); }                            // device [V][combs]
+    double *apFb() { return afb_.get(); }                               // device [V][allpasses]
+
+private:
+    struct Layout {
+        std::vector<uint32_t> combs, aps, lowp, off;
+        uint32_t S = 0;
+        Layout(const std::vector<uint32_t> &c, const std::vector<uint32_t> &a, const std::vector<uint32_t> &l) : combs(c), aps(a), lowp(l) {
+            if (lowp.empty()) lowp.assign(combs.size(), 0);
+            if (lowp.size() != combs.size()) throw std::runtime_error("maxiReverbNetBank: one low-pass flag per comb");
+            off.assign(combs.size() + aps.size() + 1, 0);
+            maxigpu::check(mxg_revnet_layout_host((uint32_t)combs.size(), (uint32_t)aps.size(), combs.data(), aps.data(), lowp.data(),
+                                                  combs.size() + aps.size() <= 2 * MXG_REVNET_MAX_STAGES ? off.data() : nullptr, &S),
+                           "mxg_revnet_layout_host");
+            off.resize(combs.size() + aps.size());
+        }
+        size_t P() const { return combs.size(); }
+        size_t A() const { return aps.size(); }
+        size_t F() const { return combs.size() + aps.size(); }
+    };
+    void put(maxigpu::DeviceArray<double> &d, size_t stages, const std::vector<double> &h) {
+        if (h.size() != V * stages) throw std::runtime_error("maxiReverbNetBank: a parameter array holds [voices][stages] values");
+        maxigpu::check(mxg_sync(), "mxg_sync");  // a call still running reads the old values
+        if (!h.empty()) d.upload(h.data(), h.size());
+    }
+    void fill(maxigpu::DeviceArray<double> &d, size_t stages, double value) { put(d, stages, std::vector<double>(V * stages, value)); }
+    size_t V;
+    Layout lay_;
+    maxigpu::DeviceArray<double> rings_;
+    maxigpu::DeviceArray<int32_t> idx_;
+    maxigpu::DeviceArray<double> lp_, cfb_, cut_, afb_;
+};
+
 // ---- maxiDynamics (H:2625-2897) / maxiRMS (H:2579-2616) banks (K12): block-rate parameters per voice ------------------------
 // (per-sample parameters: call mxg_dynamics_render with ps_flags).  Rings slot-major, [capacity][V]; the defaults are the
 // reference's (500 ms and 1 s of samples at the sample rate in force at construction).  Times in ms as in the reference; the four

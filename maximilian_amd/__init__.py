@@ -10,7 +10,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiVoiceBank, maxiMixBank, maxiDelaylineBank, maxiSampleBank, maxiDCBlockerBank,
                     maxiSVFBank, maxiBiquadBank, maxiEnvGenBank, maxiSamplerBank, maxiFlangerBank, maxiChorusBank, maxiDynamicsBank,
                     maxiRMSBank, maxiSatReverbBank, maxiFreeVerbBank, maxiFreeVerbStereoBank, reverb_layout, maxiDattaroReverbBank,
-                    dattaro_layout, maxiSeqBank, maxiTriggerBank, maxiCounterBank, maxiStepBank, maxiIndexBank,
+                    dattaro_layout, maxiReverbNetBank, revnet_layout, maxiSeqBank, maxiTriggerBank, maxiCounterBank, maxiStepBank, maxiIndexBank,
                     maxiZXToPulseBank, seq_table, seq_ratio_tables, maxiAnalysisBank, maxiKuramotoBank, maxiKuramotoWideBank, envfollow_coeff, analysis_want, OSC_WAVEFORMS,
                     maxiShaperBank, maxiXFadeBank, maxiSelectBank, maxiLineBank, atan_norm, SHAPE_MODES,
                     maxiDynBank, maxiEnvelopeBank, maxiLagExpBank, maxiMapBank, dyn_coeff, dyn_makeup, MAP_MODES, CLASSIC_PS,

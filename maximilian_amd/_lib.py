@@ -114,6 +114,8 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_dattaro_layout_host": (c_int, [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_dattaro_render": (c_int, [c_uint32, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_revnet_layout_host": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_revnet_render": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 9),
     "mxg_seq_ratio_host": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
     "mxg_seq_render": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                c_int, c_void_p, c_void_p, c_size_t, c_size_t] + [c_void_p] * 9),

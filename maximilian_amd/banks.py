@@ -915,6 +915,91 @@ class maxiDattaroReverbBank(_Bank):
         return out
 
 
+def _revnet_sizes(sizes, what):
+    a = np.asarray(list(sizes), dtype=np.float64).reshape(-1)
+    if a.size and (not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(a < 0) or np.any(a > 0xffffffff)):
+        raise ValueError("%s: the delay lengths are whole numbers of samples" % what)
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def revnet_layout(comb_sizes, ap_sizes, comb_lowpass=None):
+    """(offsets [combs + allpasses], ring doubles per voice) of a reverb network (mxg_revnet_layout_host; needs no device).
+    Raises for a topology the kernel does not take: a count beyond 32, no stage at all, a length outside [1, 44100], a
+    low-pass comb shorter than 64."""
+    cs, aps = _revnet_sizes(comb_sizes, "comb_sizes"), _revnet_sizes(ap_sizes, "ap_sizes")
+    lowp = None
+    if comb_lowpass is not None:
+        lowp = np.ascontiguousarray(np.asarray(list(comb_lowpass)).reshape(-1) != 0, dtype=np.uint32)
+        if lowp.size != cs.size:
+            raise ValueError("comb_lowpass: one flag per comb")
+    S = ctypes.c_uint32()
+    offs = np.zeros(max(cs.size + aps.size, 1), np.uint32)
+    check(lib().mxg_revnet_layout_host(cs.size, aps.size, cs.ctypes.data, aps.ctypes.data, None if lowp is None else lowp.ctypes.data,
+                                       offs.ctypes.data if cs.size + aps.size <= 64 else None, ctypes.addressof(S)),
+          "mxg_revnet_layout_host")
+    return offs[:cs.size + aps.size].astype(int).tolist(), S.value
+
+
+class maxiReverbNetBank(_Bank):
+    """V custom reverbs out of maxiReverbFilters stages (libs/maxiReverb.h, K30), one topology per bank: the parallel combs
+    `comb_sizes` summed in order -- combfb, or lpcombfb where `comb_lowpass` flags it -- into the serial allpasses `ap_sizes`.
+    Lengths are whole samples in [1, 44100], at most 32 of each kind, a low-pass comb at least 64.  `play(x)` -> [N, V].
+    Feedbacks and cutoffs are per voice and stage (a scalar, [stages] or [V][stages]), constant within a call, and nothing
+    clamps them.  State: rings [V][ring_doubles] (voice-major, stage f at offsets[f], combs first), idx int32
+    [V][combs + allpasses], lp [V][combs] (the low-pass combs' filter states); all zero when fresh."""
+
+    def __init__(self, voices, comb_sizes, ap_sizes, comb_lowpass=None, comb_fb=0.85, comb_cut=0.2, ap_fb=0.85, stream=None):
+        super().__init__(voices, stream)
+        self._cs, self._as = _revnet_sizes(comb_sizes, "comb_sizes"), _revnet_sizes(ap_sizes, "ap_sizes")
+        self.ncombs, self.nallpasses = int(self._cs.size), int(self._as.size)
+        self.comb_lowpass = [False] * self.ncombs if comb_lowpass is None else [bool(f) for f in comb_lowpass]
+        self.offsets, self.ring_doubles = revnet_layout(self._cs, self._as, self.comb_lowpass)
+        self._lowp = np.asarray(self.comb_lowpass, dtype=np.uint32)
+        self.lengths = self._cs.astype(int).tolist() + self._as.astype(int).tolist()
+        self.rings = DeviceBuffer((self.V, self.ring_doubles))
+        self.idx = DeviceBuffer((self.V, self.ncombs + self.nallpasses), np.int32)
+        self.lp = DeviceBuffer((self.V, self.ncombs))
+        self.comb_fb = DeviceBuffer((self.V, self.ncombs))
+        self.comb_cut = DeviceBuffer((self.V, self.ncombs))
+        self.ap_fb = DeviceBuffer((self.V, self.nallpasses))
+        self.set_comb_fb(comb_fb)
+        self.set_comb_cut(comb_cut)
+        self.set_ap_fb(ap_fb)
+
+    def _set(self, buf, value, stages, what):
+        a = np.asarray(value, dtype=np.float64)
+        if a.ndim > 2 or (a.ndim == 1 and a.shape != (stages,)) or (a.ndim == 2 and a.shape != (self.V, stages)):
+            raise ValueError("%s: a scalar, [%d] or [%d][%d], got %s" % (what, stages, self.V, stages, a.shape))
+        self.sync()  # a call still running reads the old values
+        buf.upload(np.broadcast_to(a, (self.V, stages)))
+
+    def set_comb_fb(self, fb):
+        self._set(self.comb_fb, fb, self.ncombs, "comb_fb")
+
+    def set_comb_cut(self, cutoff):
+        self._set(self.comb_cut, cutoff, self.ncombs, "comb_cut")
+
+    def set_ap_fb(self, fb):
+        self._set(self.ap_fb, fb, self.nallpasses, "ap_fb")
+
+    def clear(self):
+        """Back to fresh objects: rings, indices and low-pass states zero; the parameters stay."""
+        self.sync()
+        for b in (self.rings, self.idx, self.lp):
+            if b.nbytes:
+                check(lib().mxg_memset(b.ptr, 0, b.nbytes, None), "mxg_memset")
+        check(lib().mxg_stream_sync(None), "mxg_stream_sync")
+
+    def play(self, x, out=None):
+        N = x.shape[0]
+        _fx_input(x, self.V, N)
+        out = self._out(N, out)
+        check(lib().mxg_revnet_render(self.ncombs, self.nallpasses, self._cs.ctypes.data, self._as.ctypes.data, self._lowp.ctypes.data,
+                                      self.V, N, _ptr(x), self.comb_fb.ptr, self.comb_cut.ptr, self.ap_fb.ptr, self.rings.ptr,
+                                      self.idx.ptr, self.lp.ptr, _ptr(out), self.stream), "mxg_revnet_render")
+        return out
+
+
 DYN_PS = {"thresholdHigh": 1, "ratioHigh": 2, "kneeHigh": 4, "thresholdLow": 8, "ratioLow": 16, "kneeLow": 32}  # MXG_DYN_PS_*
 
 
