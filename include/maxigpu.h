@@ -1540,6 +1540,36 @@ int mxg_mixq_release(mxg_mixq *q, void *stream);
 int mxg_scan_long_render(int kind, size_t V, size_t N, const double *d_in, const double *d_coef, double *d_st, double *d_out, void *stream);
 int mxg_scan_long_host(int kind, size_t V, size_t N, const double *h_in, const double *h_coef, double *h_st, double *h_out);
 
+/* ---- the same with PER-SAMPLE coefficients: a time-varying scan (K31) -------------------------------------------------------
+ * mxg_scan_long_render_swept: mxg_scan_long_render for a filter whose coefficients move every sample -- kind 3 lores, 4 hires,
+ * 5 maxiLagExp, the kinds that have a sequential per-sample entry point (mxg_filter_render_coefs; mxg_lag_render with
+ * alpha_per_sample = 1) to hand a stream to and from.  Kinds 0-2 have no swept form: MXG_ERR_INVALID, and the message says so.
+ *   d_coef_ps  [N][coef_rows][V], coef_rows 2 ... 8; rows 0 and 1 are read: (c, r) of mxg_filter_coeffs_host, or (alpha,
+ *              alphaReciprocal).  The [N][3][V] array of mxg_filter_render_coefs is taken as it is with coef_rows = 3; a caller who
+ *              minds the traffic packs 2 rows.
+ *   d_st       as mxg_scan_long_render for the kind: [5][V], rows 0-1 read and written, rows 2-4 left as they are; [1][V] for the lag.
+ * V 1 ... 4096, N 1 ... 2^28.  d_out == d_in is allowed; a partial overlap of the two, any overlap of d_out with d_coef_ps and null
+ * pointers are refused (before the device is touched).  The signal is cut into chunks of 1024 samples; every chunk and every lane
+ * carries an affine pair (M, e) of its own, composed by scans: three launches on `stream`, no workgroup waiting on another.  One
+ * state array can alternate between this entry point, mxg_scan_long_render and the sequential entry points of the kind.
+ * A TOLERANCE mode as mxg_scan_long_render: |error| <= SWEPT_RTOL x the voice's peak of the sequential output, for sweeps whose
+ * sequential float64 output is finite with peak <= 1e6 (cutoffs inside 10 Hz ... 8 kHz) and finite input, measured on the host twin
+ * over the sweep set of tests/scan_long_swept_host.py (LFOs, ramps, steps; resonance 1 ... 1000 and swept; alpha 1e-6 ... 1) at 2, 66
+ * and 4097 chunks and a ragged N, and over the constant scan's full-domain settings HELD still at 66 and 4097 chunks, three carried
+ * calls -> the bound (worst x 2, one digit, rounded up; tools/measure_longsweep_tolerance.py, profiles/longsweep_tolerance.json,
+ * DESIGN.md K31):
+ *     lores 2.8e-12 -> 6e-12    hires 2.8e-12 -> 6e-12    maxiLagExp 2.1e-12 -> 5e-12
+ * The worst are barely-damped settings that stand still (10 Hz at resonance 1000; alpha 1e-6); their error stops growing once the
+ * stream is longer than the setting's memory, so the bound does not depend on the length (measured to 1.26e7 samples per voice).
+ * Over sweeps that move the figure is 4e-14, the float64 sequential recurrence's own distance from a long-double one.  A cutoff
+ * stepping at random at resonance >= 100 diverges in the reference itself and is outside the set.
+ * N < 64 is plain steps: the sequential recurrence's bits.  Non-finite input: as mxg_scan_long_render.
+ * mxg_scan_long_swept_host: the same arithmetic on host arrays -- the device gives these bits. */
+int mxg_scan_long_render_swept(int kind, size_t V, size_t N, const double *d_in, const double *d_coef_ps, size_t coef_rows,
+                               double *d_st, double *d_out, void *stream);
+int mxg_scan_long_swept_host(int kind, size_t V, size_t N, const double *h_in, const double *h_coef_ps, size_t coef_rows,
+                             double *h_st, double *h_out);
+
 /* (The bandwidth-probe kernels bench.py and tools/ measure ceilings with are NOT part of this ABI: include/maxicalib.h,
  * libmaxicalib.so -- measurement code, built beside the product library.) */
 

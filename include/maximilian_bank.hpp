@@ -2635,6 +2635,8 @@ private:
 // that a scan joins.  A tolerance mode (maxigpu.h: SCAN_LONG_RTOL per kind), not bit-exact against the sequential banks.  The state
 // rows are those of the sequential entry point of the kind ([3][V], [5][V] or [1][V]): state() / set_state() hand a stream over to
 // one and back.  V = 1 filters a plain contiguous signal, e.g. maxiLooperBank::deviceSamples(r); d_out == d_in is allowed.
+// LORES, HIRES and LAG banks also take coefficients that move every sample (mxg_scan_long_render_swept, K31): processSwept /
+// hostSwept, on the same state; sweepCoefficients makes the [N][3][V] array from a cutoff and a resonance per sample.
 class maxiLongScanBank {
 public:
     enum Kind { DC = 0, SVF = 1, BIQUAD = 2, LORES = 3, HIRES = 4, LAG = 5 };
@@ -2678,6 +2680,26 @@ public:
     void host(size_t N, const double *h_in, double *h_out, std::vector<double> &st) const {
         if (coef_.empty() || st.size() != state_rows() * V) throw std::logic_error("maxiLongScanBank::host: coefficients and a whole state array");
         maxigpu::check(mxg_scan_long_host((int)kind_, V, N, h_in, coef_.data(), st.data(), h_out), "mxg_scan_long_host");
+    }
+    // The same with the coefficients of every sample (mxg_scan_long_render_swept, K31; LORES, HIRES and LAG): d_coef_ps
+    // [N][coef_rows][V] on the device, coef_rows 2 ... 8, rows 0-1 read.  Shares the bank's state with process(); needs no setter.
+    void processSwept(size_t N, const double *d_in, const double *d_coef_ps, size_t coef_rows, double *d_out, void *stream = nullptr) {
+        maxigpu::check(mxg_scan_long_render_swept((int)kind_, V, N, d_in, d_coef_ps, coef_rows, d_st_.get(), d_out, stream), "mxg_scan_long_render_swept");
+    }
+    // its host twin (the device's bits) on host arrays from the state `st` [state_rows()][V], which it advances
+    void hostSwept(size_t N, const double *h_in, const double *h_coef_ps, size_t coef_rows, double *h_out, std::vector<double> &st) const {
+        if (st.size() != state_rows() * V) throw std::logic_error("maxiLongScanBank::hostSwept: a whole state array");
+        maxigpu::check(mxg_scan_long_swept_host((int)kind_, V, N, h_in, h_coef_ps, coef_rows, st.data(), h_out), "mxg_scan_long_swept_host");
+    }
+    // host [N][3][V] for LORES / HIRES from cutoff and res [N][V]: mxg_filter_coeffs_host per sample, rows c, r, 0 -- what
+    // mxg_filter_render_coefs takes, and processSwept with coef_rows = 3
+    static std::vector<double> sweepCoefficients(Kind kind, size_t N, size_t V, const std::vector<double> &cutoff, const std::vector<double> &res) {
+        if (kind != LORES && kind != HIRES) throw std::invalid_argument("maxiLongScanBank::sweepCoefficients: LORES or HIRES");
+        if (cutoff.size() != N * V || res.size() != N * V) throw std::invalid_argument("maxiLongScanBank::sweepCoefficients: cutoff and res are [N][V]");
+        std::vector<double> c(3 * N * V);
+        for (size_t n = 0; n < N; n++)
+            maxigpu::check(mxg_filter_coeffs_host(0, V, cutoff.data() + n * V, res.data() + n * V, c.data() + n * 3 * V), "mxg_filter_coeffs_host");
+        return c;
     }
     std::vector<double> state() const {
         maxigpu::check(mxg_sync(), "mxg_sync");

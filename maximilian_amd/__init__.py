@@ -17,7 +17,7 @@ from .banks import (DeviceBuffer, maxiSettings, maxiOscBank, maxiFilterBank, max
                     maxiPolyBLEPBank, polyblep_sync, POLYBLEP_WAVEFORMS,
                     maxiKickBank, maxiSnareBank, maxiHatsBank, maxiClockBank, DRUM_KINDS,
                     maxiAtomBank, ATOM_KINDS, ATOM_ONSETS, maxiLooperBank, LOOPER_PLAY, maxiLongScanBank, LONG_SCAN_KINDS,
-                    FILTER_KINDS, SAMPLE_MODES)
+                    sweep_lores, sweep_hires, sweep_lag, FILTER_KINDS, SAMPLE_MODES)
 from .spectral import (maxiConvolve, maxiConvolveBank, maxiFFT, maxiIFFT, maxiFFTBank, maxiIFFTBank, spectral_bank_plan, maxiMFCC, maxiBarkBatch, maxiOctaveBatch, frames_in_stream,  # noqa: F401
                        padded_stream)
 from .grains import maxiTimeStretchBank, maxiStretchBank, maxiPitchShiftBank, maxiGrainPoolBank, WINDOWS  # noqa: F401

@@ -147,6 +147,8 @@ SIGNATURES = {
     "mxg_lag_host": (c_int, [c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mxg_scan_long_render": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mxg_scan_long_host": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mxg_scan_long_render_swept": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mxg_scan_long_swept_host": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mxg_map_range_host": (c_int, [c_int, c_size_t, c_void_p, c_void_p]),
     "mxg_map_render": (c_int, [c_int, c_size_t, c_size_t] + [c_void_p] * 5),
     "mxg_map_host": (c_int, [c_int, c_size_t, c_size_t] + [c_void_p] * 4),

@@ -2596,7 +2596,13 @@ class maxiLongScanBank:
     samples that a scan joins.  A tolerance mode (include/maxigpu.h: SCAN_LONG_RTOL per kind), not bit-exact against the
     sequential banks; the state rows are those of the sequential bank of the kind ([3][V], [5][V] or [1][V]), so set_state() /
     state() hand a stream over to one and back.  V = 1 filters a plain contiguous signal: a maxiLooperBank slot_pointer, an uploaded
-    maxiSample.  The device is first touched by process(); the setters, state() before it and host() need none."""
+    maxiSample.  The device is first touched by process(); the setters, state() before it and host() need none.
+
+    A lores, hires or lag bank also takes coefficients that move every sample (mxg_scan_long_render_swept, K31): process_swept(x,
+    coef_ps) / host_swept(x, coef_ps) with coef_ps [N][rows][V] from sweep_lores / sweep_hires / sweep_lag (or mxg_filter_render_coefs'
+    own [N][3][V] array), chunks of 1024 samples, every lane and chunk carrying its own transition; SWEPT_RTOL per kind in
+    include/maxigpu.h.  They share the state with process() / host() and with the sequential per-sample entry points, and need no
+    setter; on a dc, svf or biquad bank they raise ValueError."""
 
     def __init__(self, voices, kind, stream=None):
         self.V = int(voices)
@@ -2699,3 +2705,91 @@ class maxiLongScanBank:
 
     def sync(self):
         check(lib().mxg_stream_sync(self.stream), "mxg_stream_sync")
+
+    # ---- per-sample coefficients (mxg_scan_long_render_swept, K31) ---------------------------------------------------------------
+    def _need_swept(self, what):
+        if self.kind not in (3, 4, 5):
+            raise ValueError("maxiLongScanBank.%s: kind %d has no swept form (lores, hires and lag have)" % (what, self.kind))
+
+    def _coef_rows(self, coef_ps, N):
+        """coef_ps [N][rows][V] -> rows (a raw pointer cannot say: it is taken as packed, 2 rows)."""
+        if not hasattr(coef_ps, "shape"):
+            return 2
+        shape = tuple(int(s) for s in coef_ps.shape)
+        n = int(np.prod(shape))
+        if len(shape) == 3:
+            return shape[1]
+        if N and n % (N * self.V) == 0:
+            return n // (N * self.V)
+        raise ValueError("maxiLongScanBank: coef_ps is [N][rows][V]")
+
+    def process_swept(self, x, coef_ps, N=None, out=None, coef_rows=None):
+        """process() with the coefficients of every sample: coef_ps [N][rows][V] (sweep_lores / sweep_hires / sweep_lag make them on
+        the host), rows 2 ... 8, rows 0-1 read -- numpy (uploaded), a DeviceBuffer / torch tensor, or a raw device address with
+        coef_rows (default 2).  Shares the bank's state with process(); needs no constant coefficients set."""
+        self._need_swept("process_swept")
+        check(lib().mxg_init(-1), "mxg_init")
+        if isinstance(x, np.ndarray):
+            x = DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float64).reshape(-1, self.V))
+        if N is None:
+            if not hasattr(x, "shape"):
+                raise ValueError("maxiLongScanBank.process_swept: a raw pointer needs N")
+            N = int(x.shape[0]) if len(x.shape) > 1 or self.V > 1 else int(np.prod(x.shape))
+        N = int(N)
+        rows = int(coef_rows) if coef_rows is not None else self._coef_rows(coef_ps, N)
+        if isinstance(coef_ps, np.ndarray):
+            coef_ps = DeviceBuffer.from_numpy(np.ascontiguousarray(coef_ps, np.float64))
+        if out is None:
+            out = DeviceBuffer((N, self.V), np.float64, zero=False)
+        if self._dst is None:
+            self._dst = DeviceBuffer.from_numpy(self._st)
+        check(lib().mxg_scan_long_render_swept(self.kind, self.V, N, _ptr(x), _ptr(coef_ps), rows, self._dst.ptr, _ptr(out), self.stream),
+              "mxg_scan_long_render_swept")
+        self._keep = (x, coef_ps, out)   # (alive until the stream has run the launches)
+        return out
+
+    def host_swept(self, x, coef_ps, advance=False):
+        """The host twin (mxg_scan_long_swept_host, the device's bits) on numpy x [N][V], coef_ps [N][rows][V] from the bank's state:
+        (out, the state after it).  advance: the bank's state becomes that state."""
+        self._need_swept("host_swept")
+        a = np.ascontiguousarray(x, np.float64).reshape(-1, self.V)
+        c = np.ascontiguousarray(coef_ps, np.float64)
+        rows = self._coef_rows(c, a.shape[0])
+        st, out = self.state(), np.empty_like(a)
+        check(lib().mxg_scan_long_swept_host(self.kind, self.V, a.shape[0], a.ctypes.data, c.ctypes.data, rows, st.ctypes.data, out.ctypes.data),
+              "mxg_scan_long_swept_host")
+        if advance:
+            self.set_state(st)
+        return out, st
+
+
+def _sweep_filter(cutoff, res):
+    cu, rs = np.broadcast_arrays(np.asarray(cutoff, np.float64), np.asarray(res, np.float64))
+    if cu.ndim != 2:
+        raise ValueError("sweep_lores / sweep_hires: cutoff and res broadcast to [N][V]")
+    N, V = cu.shape
+    cu, rs = np.ascontiguousarray(cu).ravel(), np.ascontiguousarray(rs).ravel()
+    c = np.zeros((3, N * V))
+    check(lib().mxg_filter_coeffs_host(0, N * V, cu.ctypes.data, rs.ctypes.data, c.ctypes.data), "mxg_filter_coeffs_host")
+    return np.ascontiguousarray(c.reshape(3, N, V).transpose(1, 0, 2))
+
+
+def sweep_lores(cutoff, res):
+    """Per-sample lores coefficients for maxiLongScanBank.process_swept: cutoff, res [N][V] (or broadcastable to it) through
+    mxg_filter_coeffs_host -> host [N][3][V], rows c, r, 0: what mxg_filter_render_coefs takes, unchanged."""
+    return _sweep_filter(cutoff, res)
+
+
+def sweep_hires(cutoff, res):
+    """As sweep_lores (lores and hires share c and r, C:456-461 / C:471-476)."""
+    return _sweep_filter(cutoff, res)
+
+
+def sweep_lag(alpha, alphaReciprocal=None):
+    """Per-sample maxiLagExp coefficients: alpha [N][V], alphaReciprocal = 1 - alpha unless given -> host [N][2][V]."""
+    a = np.asarray(alpha, np.float64)
+    r = 1.0 - a if alphaReciprocal is None else np.asarray(alphaReciprocal, np.float64)
+    a, r = np.broadcast_arrays(a, r)
+    if a.ndim != 2:
+        raise ValueError("sweep_lag: alpha is [N][V]")
+    return np.ascontiguousarray(np.stack([a, r], axis=1))

@@ -61,7 +61,7 @@ inline int rw_store_choice(size_t V, size_t N, const void *d_out, RwFamily fam =
 // Library-owned scratch, one grow-only buffer per (slot, stream): launches on different streams never share
 // (or resize) each other's temporaries; launches on one stream are ordered by the stream.  Returns MXG_OK and
 // a device pointer of at least `bytes`.
-enum ScratchSlot { SCR_MIX_GAINS, SCR_OSC_MIX, SCR_GRAIN_ERR, SCR_GRAIN_SCHED, SCR_IFFT_OUT, SCR_IFFT_BUF, SCR_MFCC_RAW, SCR_CONVOLVE, SCR_GRAIN_MIX, SCR_PART_SYNC, SCR_OSCTAB_MARKS, SCR_OSCTAB_MARKS2, SCR_OSCTAB_CARRY, SCR_OSCTAB_SUM, SCR_VOICE_PACE, SCR_OSC_PACE, SCR_SMP_PACE, SCR_CONVOLVE_BANK, SCR_LOOPER, SCR_SCAN_LONG, SCR_SPECTRAL_BANK, SCR_SPECTRAL_BANK_IO, SCR_SLOTS };
+enum ScratchSlot { SCR_MIX_GAINS, SCR_OSC_MIX, SCR_GRAIN_ERR, SCR_GRAIN_SCHED, SCR_IFFT_OUT, SCR_IFFT_BUF, SCR_MFCC_RAW, SCR_CONVOLVE, SCR_GRAIN_MIX, SCR_PART_SYNC, SCR_OSCTAB_MARKS, SCR_OSCTAB_MARKS2, SCR_OSCTAB_CARRY, SCR_OSCTAB_SUM, SCR_VOICE_PACE, SCR_OSC_PACE, SCR_SMP_PACE, SCR_CONVOLVE_BANK, SCR_LOOPER, SCR_SCAN_LONG, SCR_SPECTRAL_BANK, SCR_SPECTRAL_BANK_IO, SCR_SCAN_LONG_SWEPT, SCR_SLOTS };
 int scratch_get(ScratchSlot slot, hipStream_t st, size_t bytes, void **out, bool *fresh = nullptr);  // *fresh: newly allocated (contents undefined)
 unsigned pace_start_period(size_t bytes);  // a paced launch's starting period in ticks of the device's constant counter (runtime.hip); 0 = do not pace
 unsigned *pace_words(ScratchSlot slot, hipStream_t st, size_t nwords);  // a pace controller's words (runtime.hip), or null inside a capture

@@ -81,6 +81,21 @@ MXG_HD M3 square(const M3 &A) {
         for (int j = 0; j < 3; j++) R.m[i][j] = A.m[i][0] * A.m[0][j] + A.m[i][1] * A.m[1][j] + A.m[i][2] * A.m[2][j];
     return R;
 }
+// A * B over the leading D x D block (D = 3: the general product; the entries outside the block are neither read nor written)
+template <int D = 3>
+MXG_HD M3 product(const M3 &A, const M3 &B) {
+    M3 R = {};
+    MXG_SCAN_UNROLL
+    for (int i = 0; i < D; i++)
+        MXG_SCAN_UNROLL
+        for (int j = 0; j < D; j++) {
+            double t = A.m[i][0] * B.m[0][j];
+            MXG_SCAN_UNROLL
+            for (int k = 1; k < D; k++) t = t + A.m[i][k] * B.m[k][j];
+            R.m[i][j] = t;
+        }
+    return R;
+}
 
 // The basis the scan is carried in.  maxiBiquad with both poles near z = 1 (a 20 ... 60 Hz cutoff): the direct-form-II states reach
 // ~1 / (1 + b1 + b2) times the input (1e5 at 20 Hz) with v1 ~ v2, and the entries of A^n grow like n, so M * (v0, v1, v2) forms
